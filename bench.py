@@ -1,8 +1,18 @@
 #!/usr/bin/env python3
 """bench.py --gpus N --steps K --warmup W [--scaling strong|weak] [--lg 26 | --total-lg 28]
+           [--dump-outputs DIR] [--full]
 
 Headline (BASELINE.json metric): BLS12-381 G1 Pippenger MSM of 2^26 points, inputs resident in
 HBM, on N GPUs of one node.  A step = one full MSM.
+
+A plain run sets up, warms up, times the K steps and prints the JSON line (headline, ms_per_step,
+and the roofline of k_accumulate read off the library's own timers during those steps).
+--dump-outputs DIR writes the result of the last timed step as DIR/msm_affine.npy: the affine
+(x, y) of the MSM, each coordinate as 12 little-endian 32-bit words stored exactly in float64,
+shape (2, 12); the point at infinity is all zero.  Inputs depend on the arguments only.
+--full adds everything else below: the checker of the last timed result against the oracle, the
+NTT section, the extras and the CPU baseline (--no-ntt / --no-extras / --no-cpu-baseline leave
+one out); without --full the keys "parity", "ntt", "extras" and "cpu_baseline" are null.
 
   N = 1                 2^26 points on one GPU (configs[2])
   N > 1, default        STRONG scaling: the SAME 2^26-point MSM cut into N contiguous shards, one
@@ -122,6 +132,10 @@ def main():
     ap.add_argument("--lg", type=int, default=26, help="log2 points: of the whole MSM (strong) / per GPU (weak)")
     ap.add_argument("--total-lg", type=int, default=None, help="strong scaling with 2^TOTAL_LG points in total (configs[3]: 28)")
     ap.add_argument("--scaling", choices=("strong", "weak"), default="strong")
+    ap.add_argument("--full", action="store_true",
+                    help="also the oracle checker of the last timed step, the NTT section, the extras and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result (affine x, y as 32-bit words in float64) to DIR/msm_affine.npy")
     ap.add_argument("--ntt-lg", type=int, default=24)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ntt", action="store_true")
@@ -206,33 +220,40 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)                # every step: the slowest rank's time
         elapsed = float(t[0].item()); step_ms = [float(v) for v in t[1:]]
 
-    # ---- CHECKER (outside the timed region): the last timed result against the oracle ------------
+    if rank == 0 and args.dump_outputs:
+        # the last timed result in its canonical form (a Jacobian X|Y|Z is not unique): affine x | y, 32-bit words, exact in float64
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        xy = sppark_amd.to_affine(result).view("<u4").astype(np.float64).reshape(2, -1)
+        np.save(os.path.join(args.dump_outputs, "msm_affine.npy"), xy)
+
+    # ---- CHECKER (outside the timed region, --full): the last timed result against the oracle ----
     # class sums of this rank's scalars (exact integer arithmetic), gathered over the ranks; rank 0
     # evaluates the folded 2048-point MSM with the oracle and compares affine coordinates bit for bit
-    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
-    import oracle as O                                          # checker / cpu_baseline legs only
-    from oracle import fold
-    r_mod = O.FR_MODULUS[O.BLS12_381]
-    folded = fold.fold_scalars(sc, PERIOD, r_mod)
-    if use_dist:
-        allf = multi_gpu.all_gather_bytes(folded.reshape(-1)).reshape(-1, PERIOD, 32)
-    else:
-        allf = folded.reshape(1, PERIOD, 32)
     parity = None
-    if rank == 0:
-        tot = np.zeros((PERIOD, 32), dtype=np.uint8)
-        for j in range(PERIOD):
-            v = sum(int.from_bytes(allf[k, j].tobytes(), "little") for k in range(allf.shape[0])) % r_mod
-            tot[j] = np.frombuffer(v.to_bytes(32, "little"), dtype=np.uint8)
-        expect = O.msm_affine(O.BLS12_381, base.cpu().numpy(), tot, algo=0, param=8)
-        got = sppark_amd.to_affine(result)
-        parity = {"timed_msm_equals_oracle": bool((got == expect).all()),
-                  "how": "last timed result, affine, vs oracle MSM of the 2048 distinct points with the exactly folded scalars (oracle/fold.py)",
-                  "result_affine_sha256": hashlib.sha256(got.tobytes()).hexdigest()}
-        assert parity["timed_msm_equals_oracle"], "timed MSM result differs from the oracle"
+    if args.full:
+        sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+        import oracle as O                                      # checker / cpu_baseline legs only
+        from oracle import fold
+        r_mod = O.FR_MODULUS[O.BLS12_381]
+        folded = fold.fold_scalars(sc, PERIOD, r_mod)
+        if use_dist:
+            allf = multi_gpu.all_gather_bytes(folded.reshape(-1)).reshape(-1, PERIOD, 32)
+        else:
+            allf = folded.reshape(1, PERIOD, 32)
+        if rank == 0:
+            tot = np.zeros((PERIOD, 32), dtype=np.uint8)
+            for j in range(PERIOD):
+                v = sum(int.from_bytes(allf[k, j].tobytes(), "little") for k in range(allf.shape[0])) % r_mod
+                tot[j] = np.frombuffer(v.to_bytes(32, "little"), dtype=np.uint8)
+            expect = O.msm_affine(O.BLS12_381, base.cpu().numpy(), tot, algo=0, param=8)
+            got = sppark_amd.to_affine(result)
+            parity = {"timed_msm_equals_oracle": bool((got == expect).all()),
+                      "how": "last timed result, affine, vs oracle MSM of the 2048 distinct points with the exactly folded scalars (oracle/fold.py)",
+                      "result_affine_sha256": hashlib.sha256(got.tobytes()).hexdigest()}
+            assert parity["timed_msm_equals_oracle"], "timed MSM result differs from the oracle"
 
     ntt = None
-    if rank == 0 and not args.no_ntt:
+    if args.full and rank == 0 and not args.no_ntt:
         lg = args.ntt_lg
         g = torch.Generator(device="cuda"); g.manual_seed(2)
         x = (torch.randint(0, 2**62, (1 << lg,), dtype=torch.int64, device="cuda", generator=g))   # < p
@@ -357,7 +378,7 @@ def main():
                             "note": "whole forward transform vs 16 B/element algorithmic (one read + one write of the array)" + ntt_traffic_note}}
 
     extras = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         extras = {}
         # BASELINE configs[4]: alt_bn128 G1 MSM + BabyBear NTT (multi-field instantiation)
         bpts, bbase = synth.replicated_points(n, "bn254", PERIOD, 7)
@@ -578,7 +599,7 @@ def main():
         sppark_amd.ffi.load("bls12_381").sppark_msm_release_cached()
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cores = len(os.sched_getaffinity(0))
         # oracle/_ref (the reference's own msm/pippenger.hpp + util/thread_pool_t.hpp, compiled in place
         # by oracle/Makefile over the oracle's portable field; prebuilt, travels with the snapshot) when it

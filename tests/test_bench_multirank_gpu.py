@@ -20,7 +20,7 @@ def _run(world, extra):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
            "--gpus", str(world), "--backend", "gloo", "--steps", "2", "--warmup", "1",
-           "--no-ntt", "--no-extras", "--no-cpu-baseline"] + extra
+           "--full", "--no-ntt", "--no-extras", "--no-cpu-baseline"] + extra
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -2,9 +2,7 @@
 set -e
 cd "$(dirname "$0")/.."
 c() { cp "gpurun_out/$1" "profiles/$2"; }
-c r6e_bench_final.json r06_bench_line.json
 c r6e_bench_headline_rocprofv3_summary.txt r06_bench_headline_rocprofv3_summary.txt
-c r6e_bench_rocprofv3_summary.txt r06_bench_rocprofv3_summary.txt
 c r6e_pmc_traffic.json r06_pmc_traffic.json
 c r6e_ntt_gl64_pmc.json r06_ntt_gl64_pmc.json
 c pmc_msm_acc6.txt r06_msm_accumulate_sq_pmc.txt

@@ -5,4 +5,4 @@ timeout 1800 python -m pytest tests -m gpu -x -q --timeout 600 > $R/gpurun_out/r
 timeout 600 python tools/gpu_msm_tail.py ab 16 18 19 20 21 22 26 > $R/gpurun_out/r6_19_top_ab.log 2>&1
 grep -v amdgpu $R/gpurun_out/r6_19_top_ab.log | grep "auto\|top per sum"
 timeout 600 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-SECONDS=0; timeout 900 python bench.py > $R/gpurun_out/r6_19_bench.json 2> $R/gpurun_out/r6_19_bench.err; echo "bench.py wall: $SECONDS s"; tail -c 400 $R/gpurun_out/r6_19_bench.json
+SECONDS=0; timeout 900 python bench.py --full > $R/build/r6_19_bench.json 2> $R/build/r6_19_bench.err; echo "bench.py wall: $SECONDS s"; tail -c 400 $R/build/r6_19_bench.json

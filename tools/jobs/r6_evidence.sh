@@ -26,9 +26,9 @@ python -c "import json,sys; json.load(open('gpurun_out/r6e_pmc_traffic.json')); 
 (cd /tmp && cd $R && timeout 600 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof_r6h -o bench -- python bench.py --no-extras --no-ntt --no-cpu-baseline > $R/gpurun_out/r6e_bench_headline.json 2> $R/gpurun_out/r6e_bench_headline.err)
 python tools/rocprof_summary.py $(find gpurun_out/prof_r6h -name "*.db" | head -1) > gpurun_out/r6e_bench_headline_rocprofv3_summary.txt 2>&1
 head -24 gpurun_out/r6e_bench_headline_rocprofv3_summary.txt | cut -c1-130
-(cd /tmp && cd $R && timeout 900 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof_r6e -o bench -- python bench.py > $R/gpurun_out/r6e_bench_prof.log 2>&1); tail -c 300 $R/gpurun_out/r6e_bench_prof.log
-python tools/rocprof_summary.py $(find gpurun_out/prof_r6e -name "*.db" | head -1) $(find gpurun_out/prof_r6e_fetch -name "*.db" | head -1) $(find gpurun_out/prof_r6e_write -name "*.db" | head -1) > gpurun_out/r6e_bench_rocprofv3_summary.txt 2>&1
-head -34 gpurun_out/r6e_bench_rocprofv3_summary.txt | cut -c1-140
+(cd /tmp && cd $R && timeout 900 rocprofv3 --kernel-trace --stats -d $R/build/prof_r6e_full -o bench -- python bench.py --full > $R/build/r6e_bench_prof.log 2>&1); tail -c 300 $R/build/r6e_bench_prof.log
+python tools/rocprof_summary.py $(find build/prof_r6e_full -name "*.db" | head -1) $(find . -path "*/prof_r6e_fetch/*.db" | head -1) $(find . -path "*/prof_r6e_write/*.db" | head -1) > profiles/r06_bench_rocprofv3_summary.txt 2>&1
+head -34 profiles/r06_bench_rocprofv3_summary.txt | cut -c1-140
 for lg in 26 16 12; do
   rm -rf gpurun_out/prof_tl
   (cd /tmp && cd $R && timeout 300 rocprofv3 --kernel-trace -d $R/gpurun_out/prof_tl -o tl -- python tools/gpu_msm_tail.py ab $lg > $R/gpurun_out/r6e_tl.log 2>&1)
@@ -40,7 +40,7 @@ python tools/rocprof_timeline.py $(find gpurun_out/prof_tl -name "*.db" | head -
 rm -f gpurun_out/pmc_msm_acc6.txt gpurun_out/pmc_bn254_acc6.txt
 bash tools/gpu_pmc_job.sh msm_acc6 "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU|SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY" -- python tools/gpu_msm_one.py 26 0 | grep -i "accumulate\|convert\|kernel "
 bash tools/gpu_pmc_job.sh bn254_acc6 "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU" -- python tools/gpu_msm_bn254.py 26 | grep -i "accumulate\|kernel "
-SECONDS=0; timeout 900 python bench.py > $R/gpurun_out/r6e_bench_final.json 2> $R/gpurun_out/r6e_bench_final.err; echo "bench.py wall: $SECONDS s" | tee $R/gpurun_out/r6e_bench_wall.txt; tail -c 600 $R/gpurun_out/r6e_bench_final.json
+SECONDS=0; timeout 900 python bench.py --full > profiles/r06_bench_line.json 2> $R/build/r6e_bench_final.err; echo "bench.py wall: $SECONDS s" | tee $R/build/r6e_bench_wall.txt; tail -c 600 profiles/r06_bench_line.json
 timeout 400 env NTT_LGS=12,16,20,22,24,26 python tools/gpu_ntt_bench.py > $R/gpurun_out/r6e_ntt_bench.log 2>&1
 timeout 400 env NTT_LGS=12,16,18,20,22,24 python tools/gpu_ntt_orders.py > $R/gpurun_out/r6e_ntt_orders.log 2>&1; grep "2^24" $R/gpurun_out/r6e_ntt_orders.log | cut -c1-220
 timeout 400 python tools/gpu_ntt_vs_reference.py > $R/gpurun_out/r6e_ntt_vs_reference.log 2>&1; grep -v amdgpu $R/gpurun_out/r6e_ntt_vs_reference.log | tail -30

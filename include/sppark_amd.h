@@ -217,7 +217,8 @@ SppError sppark_msm_tune_pipeline(sppark_msm_ctx *ctx, unsigned groups, size_t c
  * tree of a small MSM takes (0: the record list goes through k_join_runs / the fan-in tree) } */
 void sppark_msm_plan_sort(const sppark_msm_ctx *ctx, size_t npoints, unsigned out[8]);
 /* level-A sort records: 0 = 4 bytes unless sppark_msm_tune gives a slab count, 1 = 8 bytes, 2 = 4 bytes also with a given slab
- * count (the slabs are then the power of two below npoints / nslabs): record format and slab count can be varied independently */
+ * count (the slabs are then the power of two below npoints / nslabs; 8 bytes where that would exceed 129 slabs or 128 index
+ * groups): record format and slab count can be varied independently */
 SppError sppark_msm_tune_records(sppark_msm_ctx *ctx, unsigned records);
 /* chunks the last invoke was cut into / window groups the context would use for npoints */
 unsigned sppark_msm_last_chunks(const sppark_msm_ctx *ctx);

@@ -140,7 +140,7 @@ static inline msm_plan make_plan(size_t npoints, unsigned scalar_bits, const msm
     // number of slabs) and at most 128 groups.  Not with an explicit slab count (the tunable means what it says) unless
     // tunables.records = 2 asks for both (the slabs are then the power of two below n / nslabs); records = 1: never.
     p.IB = p.SH = 0; p.NG = 1;
-    if (!t.nslabs && p.LB < 16) {
+    if (t.records != 1 && (!t.nslabs || t.records == 2) && p.LB < 16) {
         const unsigned IB = 31 - p.LB;
         // (rounded DOWN: a size just above a power of two keeps its work-group count -- 2^26 + 1 points are 65 slabs of 2^20,
         // not 33 of 2^21, which would be two rounds of twice the work on 256 compute units instead of three)

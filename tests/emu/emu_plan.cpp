@@ -12,10 +12,10 @@ static void put(const msm_plan& p, unsigned out[21])
 }
 // out: {n, wbits, nwins, NB, nbits, HB, LB, NA, L, chunks_per_win, nslabs, slab_sz, F, K, K1, G, wpg, big, IB, SH, NG}
 extern "C" void emu_make_plan(size_t npoints, unsigned scalar_bits, unsigned wbits, unsigned L, unsigned F, unsigned K,
-                              unsigned nslabs, unsigned LB, unsigned groups, unsigned K1, unsigned out[21])
+                              unsigned nslabs, unsigned LB, unsigned groups, unsigned K1, unsigned records, unsigned out[21])
 {
     msm_tunables t;
-    t.wbits = wbits; t.L = L; t.F = F; t.K = K; t.nslabs = nslabs; t.LB = LB; t.groups = groups; t.K1 = K1;
+    t.wbits = wbits; t.L = L; t.F = F; t.K = K; t.nslabs = nslabs; t.LB = LB; t.groups = groups; t.K1 = K1; t.records = records;
     put(make_plan(npoints, scalar_bits, t), out);
 }
 // the automatic plan as the driver asks for it: with the device's resident k_accumulate lanes known

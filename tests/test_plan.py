@@ -18,7 +18,7 @@ def plan_lib():
     if not os.path.exists(so) or os.stat(so).st_mtime < max(os.stat(src).st_mtime, os.stat(hdr).st_mtime):
         subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-o", so, src])
     L = ctypes.CDLL(so)
-    L.emu_make_plan.argtypes = [ctypes.c_size_t] + [ctypes.c_uint] * 9 + [ctypes.POINTER(ctypes.c_uint)]
+    L.emu_make_plan.argtypes = [ctypes.c_size_t] + [ctypes.c_uint] * 10 + [ctypes.POINTER(ctypes.c_uint)]
     L.emu_make_fixed_plan.argtypes = [ctypes.c_size_t] + [ctypes.c_uint] * 3 + [ctypes.POINTER(ctypes.c_uint)]
     L.emu_make_plan_resident.argtypes = [ctypes.c_size_t, ctypes.c_uint, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint)]
     return L
@@ -27,7 +27,7 @@ def plan_lib():
 def _plan(lib, n, bits=255, **kw):
     out = (ctypes.c_uint * 21)()
     lib.emu_make_plan(n, bits, kw.get("wbits", 0), kw.get("L", 0), kw.get("F", 0), kw.get("K", 0), kw.get("nslabs", 0),
-                    kw.get("LB", 0), kw.get("groups", 0), kw.get("K1", 0), out)
+                    kw.get("LB", 0), kw.get("groups", 0), kw.get("K1", 0), kw.get("records", 0), out)
     return dict(zip(KEYS, out))
 
 
@@ -105,7 +105,44 @@ def test_tuned_plans(plan_lib):
                 for K, K1 in ((0, 0), (2, 4), (8, 16), (4, 1 << 20)):
                     for LB in (0, 1, 9, 13):
                         for groups in (0, 1, 3, 200):
-                            _check(_plan(plan_lib, n, 255, wbits=wbits, L=L, K=K, K1=K1, LB=LB, groups=groups, F=3, nslabs=5), n, 255)
+                            for records in (0, 1, 2):
+                                _check(_plan(plan_lib, n, 255, wbits=wbits, L=L, K=K, K1=K1, LB=LB, groups=groups, F=3, nslabs=5,
+                                             records=records), n, 255)
+
+
+def test_records_tunable(plan_lib):
+    """msm_tunables::records (sppark_msm_tune_records): 0 = 4-byte level-A records unless a slab count is given, 1 = 8-byte
+    records always, 2 = 4-byte records also with a given slab count, the slabs then the power of two at or below n / nslabs.
+    Everything else in the plan follows the size alone."""
+    same = ("wbits", "nwins", "HB", "LB", "L", "F", "K", "K1", "G")
+    packed = 0
+    for bits in (255, 254):
+        for lg in range(0, 31):
+            for n in {1 << lg, (1 << lg) + 1, (1 << lg) * 3 // 2 + 7, max(1, (1 << lg) - 1)}:
+                for LB in (0, 13):
+                    for nslabs in (0, 1, 5, 64, 300):
+                        p0, p1, p2 = (_plan(plan_lib, n, bits, LB=LB, nslabs=nslabs, records=r) for r in (0, 1, 2))
+                        for p in (p0, p1, p2):
+                            _check(p, n, bits)
+                            assert all(p[k] == p0[k] for k in same), (n, LB, nslabs, p, p0)
+                        assert p1["IB"] == 0 and p1["nslabs"] == (nslabs or min(64, max(n // 131072, min(8, max(1, n // 2048)))))
+                        assert p1["slab_sz"] == -(-n // p1["nslabs"])
+                        if nslabs == 0:
+                            assert p2 == p0
+                            continue
+                        assert p0["IB"] == 0 and p0["nslabs"] == nslabs
+                        # records = 2: power-of-two slabs of 2^floor(lg ceil(n / nslabs)) points (at most 2^IB), 4-byte
+                        # records wherever the bounds of level B (128 index groups) and of the slab scan (129 slabs) allow
+                        ib = 31 - p2["LB"]
+                        lgs = min((-(-n // nslabs)).bit_length() - 1, ib)
+                        ns = -(-n // (1 << lgs))
+                        ng = ((ns - 1) >> (ib - lgs)) + 1
+                        if ng <= 128 and ns <= 129:
+                            assert (p2["IB"], p2["slab_sz"], p2["nslabs"], p2["SH"], p2["NG"]) == (ib, 1 << lgs, ns, ib - lgs, ng), (n, nslabs, p2)
+                            packed += 1
+                        else:
+                            assert p2 == p0, (n, nslabs, p2)
+    assert packed > 1000
 
 
 def test_fixed_base_plans(plan_lib):

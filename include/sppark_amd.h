@@ -82,7 +82,20 @@ SppError mult_pippenger(void *out, const void *points, size_t npoints,
 /* poc/ntt-cuda/cuda/ntt_api.cu:25-36.  In-place transform of 2^lg_domain_size
  * elements.  order: NN=0 NR=1 RN=2 RR=3; direction: forward=0 inverse=1;
  * type: standard=0 coset=1 (ntt/ntt.cuh:33-36).  lg_domain_size == 0 is a
- * successful no-op (ntt/ntt.cuh:220-221). */
+ * successful no-op (ntt/ntt.cuh:220-221).  lg_domain_size above the field's
+ * 2-adicity or an order outside 0..3 fails before any memory is touched.
+ * Accepted sizes and what checks them (tests/, every order x direction x type
+ * unless a file says otherwise):
+ *   Goldilocks  lg 1..28 the reference's own build, 29..32 the closed form of
+ *               a periodic input (tests/test_ntt_range_gpu.py) + round trips
+ *   BabyBear    lg 1..27 the reference's own build (27 is its 2-adicity)
+ *   BLS12-381   lg 1..28 the reference's own build / the oracle, 29..30 the
+ *               closed form + round trips; 31..32 accepted, not checked
+ *   alt_bn128   lg 1..28 the reference's own build / the oracle (2-adicity 28)
+ *   BLS12-377,  lg 1..28 the reference's own build / the oracle; 29..32
+ *   Pallas,     accepted, not checked (32 GB and more per array); BLS12-377
+ *   Vesta       33..47 accepted, not checked (does not fit on one device)
+ * The reference's build stops at its MAX_LG_DOMAIN_SIZE (28, BabyBear 27). */
 SppError compute_ntt(size_t device_id, void *inout, uint32_t lg_domain_size,
                      int ntt_order, int ntt_direction, int ntt_type);
 

@@ -52,6 +52,9 @@ template<class Fn> static RustError guarded(Fn&& fn)
 static void ntt_any(size_t device_id, void* inout, uint32_t lg, int order, int direction, int type, hipStream_t stream)
 {
     if (lg == 0) return;
+    // the arguments are checked before anything is allocated or copied: |bytes| is only meaningful (and the caller's
+    // buffer only that large) for an lg the field accepts
+    if (lg > fr_t::TWO_ADICITY || order < 0 || order > 3) HIP_OK(hipErrorInvalidValue);
     const gpu_info& gpu = select_gpu((int)device_id);
     const size_t bytes = sizeof(fr_t) << lg;
     if (is_device_pointer(inout)) {
@@ -80,6 +83,7 @@ SPPARK_FFI RustError sppark_ntt(size_t device_id, void* inout, uint32_t lg_domai
 // ---- low-degree extension (C++-only in the reference: NTT::LDE / LDE_aux / LDE_powers / LDE_expand) ----
 static void lde_any(size_t device_id, void* inout, uint32_t lg_domain, uint32_t lg_blowup, void* aux_out, hipStream_t stream)
 {
+    if ((uint64_t)lg_domain + lg_blowup > fr_t::TWO_ADICITY) HIP_OK(hipErrorInvalidValue);     // (before the scratch and the copies)
     const gpu_info& gpu = select_gpu((int)device_id);
     const size_t dom = (size_t)1 << lg_domain, ext = dom << lg_blowup;
     const bool dev = is_device_pointer(inout), aux_dev = aux_out && is_device_pointer(aux_out);

@@ -260,7 +260,7 @@ public:
         const table_set ts = tables(gpu.hip_id, lg, inverse, stream);
         ntt_tables<F> T{ts.lo, ts.hi, ts.inner, lg, ts.h, ts.scale, nullptr}, G{ts.glo, ts.ghi, nullptr, lg, ts.h, ts.scale, nullptr};
         const size_t n = (size_t)1 << lg;
-        const unsigned egrid = (unsigned)((n + 255) / 256);
+        const unsigned egrid = (unsigned)std::min<size_t>((n + 255) / 256, (size_t)1 << 22);   // (k_coset strides past 2^30)
 
         // up to 2^11 elements (256-bit fields: 2^9): the whole transform -- permutations, coset powers and 1/n included -- by one work-group
         // in one launch (k_ntt_small, ntt_kernels.hpp)
@@ -502,7 +502,7 @@ public:
         const table_set ts = tables(gpu.hip_id, lg, 0, stream);
         ntt_tables<F> G{ts.glo, ts.ghi, nullptr, lg, ts.h, ts.scale, nullptr};
         const size_t n = (size_t)1 << lg;
-        hipLaunchKernelGGL(k_coset<F>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d, G, 1);
+        hipLaunchKernelGGL(k_coset<F>, dim3((unsigned)std::min<size_t>((n + 255) / 256, (size_t)1 << 22)), dim3(256), 0, stream, d, G, 1);
         HIP_OK(hipGetLastError());
     }
 

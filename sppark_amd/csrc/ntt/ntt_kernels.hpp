@@ -819,8 +819,9 @@ SPPARK_DEVFN void coset_item(F* data, const ntt_tables<F>& G, int bitrev, size_t
 template<class F>
 __global__ __launch_bounds__(256) void k_coset(F* data, ntt_tables<F> G, int bitrev)
 {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < ((size_t)1 << G.lg_n)) coset_item(data, G, bitrev, i);
+    // grid-stride: a launch covers at most 2^32 - 1 work items, so 2^32 elements take a smaller grid (ntt_driver.hpp egrid)
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < ((size_t)1 << G.lg_n); i += (size_t)gridDim.x * blockDim.x)
+        coset_item(data, G, bitrev, i);
 }
 
 // LDE spread (LDE_spread_distribute_powers, ntt/kernels.cu:155-237): the 2^lg_domain

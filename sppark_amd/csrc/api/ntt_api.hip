@@ -4,10 +4,13 @@
 #include "../ntt/field_select.hpp"
 namespace sppark_amd {
 #define SPPARK_NTT_EXTERN(DIF, INV, R1, R2) \
-    extern template __global__ void k_ntt_pass<ntt_fr_t, DIF, INV, R1, R2>(ntt_fr_t*, ntt_tables<ntt_fr_t>, ntt_pass);
+    extern template __global__ void k_ntt_pass<ntt_fr_t, DIF, INV, R1, R2>(ntt_fr_t*, ntt_tables<ntt_fr_t>, ntt_pass, size_t);
 SPPARK_NTT_PASS_ALL(SPPARK_NTT_EXTERN, true) SPPARK_NTT_PASS_ALL(SPPARK_NTT_EXTERN, false)
 #define SPPARK_NTT_SMALL_EXTERN(INV, LGC) \
-    extern template __global__ void k_ntt_small<ntt_fr_t, INV, LGC>(ntt_fr_t*, ntt_tables<ntt_fr_t>, ntt_tables<ntt_fr_t>, unsigned);
+    extern template __global__ void k_ntt_small<ntt_fr_t, INV, LGC>(ntt_fr_t*, ntt_tables<ntt_fr_t>, ntt_tables<ntt_fr_t>, unsigned, size_t);
+#define SPPARK_NTT_PACKED_EXTERN(INV, LG) \
+    extern template __global__ void k_ntt_small_packed<ntt_fr_t, INV, LG>(ntt_fr_t*, ntt_tables<ntt_fr_t>, ntt_tables<ntt_fr_t>, unsigned, size_t, size_t);
+SPPARK_NTT_PACKED_ALL(SPPARK_NTT_PACKED_EXTERN)
 #if defined(FEATURE_GOLDILOCKS) || defined(FEATURE_BABY_BEAR)
 SPPARK_NTT_SMALL_ALL_NARROW(SPPARK_NTT_SMALL_EXTERN)
 #else
@@ -17,7 +20,7 @@ SPPARK_NTT_SMALL_ALL_WIDE(SPPARK_NTT_SMALL_EXTERN)
 SPPARK_NTT_PASS_ALL_BIG(SPPARK_NTT_EXTERN, true) SPPARK_NTT_PASS_ALL_BIG(SPPARK_NTT_EXTERN, false)
 #else
 #define SPPARK_NTT_LAT_EXTERN(DIF, INV) \
-    extern template __global__ void k_ntt_pass_lat<ntt_fr_t, DIF, INV>(ntt_fr_t*, ntt_tables<ntt_fr_t>, ntt_pass);
+    extern template __global__ void k_ntt_pass_lat<ntt_fr_t, DIF, INV>(ntt_fr_t*, ntt_tables<ntt_fr_t>, ntt_pass, size_t);
 SPPARK_NTT_LAT_EXTERN(true, false) SPPARK_NTT_LAT_EXTERN(true, true) SPPARK_NTT_LAT_EXTERN(false, false) SPPARK_NTT_LAT_EXTERN(false, true)
 #endif
 }
@@ -25,10 +28,10 @@ SPPARK_NTT_LAT_EXTERN(true, false) SPPARK_NTT_LAT_EXTERN(true, true) SPPARK_NTT_
 #include "../ntt/ntt_r64_kernels.hpp"
 namespace sppark_amd {
 #define SPPARK_R64_EXTERN(K, DIF, INV) \
-    extern template __global__ void K<ntt_fr_t, DIF, INV>(ntt_fr_t*, ntt_r64_args<ntt_fr_t>);
+    extern template __global__ void K<ntt_fr_t, DIF, INV>(ntt_fr_t*, ntt_r64_args<ntt_fr_t>, size_t);
 SPPARK_R64_EXTERN(k_ntt6, true, false) SPPARK_R64_EXTERN(k_ntt6, true, true) SPPARK_R64_EXTERN(k_ntt6, false, false) SPPARK_R64_EXTERN(k_ntt6, false, true)
 SPPARK_R64_EXTERN(k_ntt12, true, false) SPPARK_R64_EXTERN(k_ntt12, true, true) SPPARK_R64_EXTERN(k_ntt12, false, false) SPPARK_R64_EXTERN(k_ntt12, false, true)
-extern template __global__ void k_ntt12<ntt_fr_t, false, false, true>(ntt_fr_t*, ntt_r64_args<ntt_fr_t>);
+extern template __global__ void k_ntt12<ntt_fr_t, false, false, true>(ntt_fr_t*, ntt_r64_args<ntt_fr_t>, size_t);
 }
 #endif
 #include "../ntt/ntt_driver.hpp"
@@ -134,6 +137,114 @@ SPPARK_FFI RustError sppark_lde_expand(size_t device_id, void* d_out, const void
                                                 lg_domain_size, lg_blowup, false, (hipStream_t)stream);
         if (stream == nullptr) HIP_OK(hipStreamSynchronize(nullptr));
     });
+}
+
+// ---- batched transforms (include/sppark_amd_batch.h) ----
+static constexpr size_t BATCH_CHUNK_BYTES = (size_t)256 << 20;    // SPPARK_BATCH_CHUNK_BYTES
+
+[[noreturn]] static void batch_reject(const char* what)
+{   throw hip_error(-(int)hipErrorInvalidValue, std::string(what) + ": invalid argument");   }
+// bytes of |batch| columns of |n| elements |stride| apart ((batch - 1) * stride + n elements); rejects a size_t overflow
+static size_t batch_extent(size_t batch, size_t stride, size_t n, const char* what)
+{
+    size_t e = 0;
+    if (__builtin_mul_overflow(batch - 1, stride, &e) || __builtin_add_overflow(e, n, &e) || __builtin_mul_overflow(e, sizeof(fr_t), &e))
+        batch_reject(what);
+    return e;
+}
+// a device buffer's extent must lie inside the allocation that holds its first byte
+static void check_device_extent(const void* p, size_t bytes, const char* what)
+{
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); batch_reject(what); }
+    const size_t off = (size_t)((const char*)p - (const char*)base);
+    if (off > size || bytes > size - off) batch_reject(what);
+}
+
+static void ntt_batch_any(size_t device_id, void* inout, uint32_t lg, size_t batch, size_t stride, int order, int direction, int type,
+                          hipStream_t stream)
+{
+    if (lg > fr_t::TWO_ADICITY) batch_reject("sppark_ntt_batch: lg_domain_size above the field's 2-adicity");
+    if (order < 0 || order > 3) batch_reject("sppark_ntt_batch: ntt_order outside 0..3");
+    const size_t n = (size_t)1 << lg;
+    if (stride == 0) stride = n;
+    if (stride < n) batch_reject("sppark_ntt_batch: stride below 2^lg_domain_size");
+    if (batch == 0 || lg == 0) return;
+    const size_t bytes = batch_extent(batch, stride, n, "sppark_ntt_batch: extent overflows size_t");
+    const gpu_info& gpu = select_gpu((int)device_id);
+    auto& E = ntt_engine<fr_t>::instance();
+    if (is_device_pointer(inout)) {
+        check_device_extent(inout, bytes, "sppark_ntt_batch: inout extends past its allocation");
+        E.run(gpu, (fr_t*)inout, lg, order, direction, type, stream, nullptr, batch, stride);
+        if (stream == nullptr) HIP_OK(hipStreamSynchronize(stream));
+        return;
+    }
+    // host buffer: chunks of whole columns through one packed device buffer (the gaps between columns are never copied)
+    const size_t col = n * sizeof(fr_t), cols = std::min(batch, std::max<size_t>(1, BATCH_CHUNK_BYTES / col));
+    pooled_scratch buf(cols * col);
+    fr_t* d = (fr_t*)buf.p;
+    for (size_t c0 = 0; c0 < batch; c0 += cols) {
+        const size_t k = std::min(cols, batch - c0);
+        char* h = (char*)inout + c0 * stride * sizeof(fr_t);
+        if (stride == n) HIP_OK(hipMemcpyAsync(d, h, k * col, hipMemcpyHostToDevice, stream));
+        else HIP_OK(hipMemcpy2DAsync(d, col, h, stride * sizeof(fr_t), col, k, hipMemcpyHostToDevice, stream));
+        E.run(gpu, d, lg, order, direction, type, stream, nullptr, k, n);
+        if (stride == n) HIP_OK(hipMemcpyAsync(h, d, k * col, hipMemcpyDeviceToHost, stream));
+        else HIP_OK(hipMemcpy2DAsync(h, stride * sizeof(fr_t), d, col, col, k, hipMemcpyDeviceToHost, stream));
+    }
+    HIP_OK(hipStreamSynchronize(stream));
+    buf.done();
+}
+
+static void lde_batch_any(size_t device_id, void* inout, uint32_t lg_domain, uint32_t lg_blowup, size_t batch, void* aux_out,
+                          hipStream_t stream)
+{
+    if ((uint64_t)lg_domain + lg_blowup > fr_t::TWO_ADICITY) batch_reject("sppark_lde_batch: lg_domain_size + lg_blowup above the field's 2-adicity");
+    const size_t dom = (size_t)1 << lg_domain, ext = dom << lg_blowup;
+    if (batch == 0) return;
+    const size_t ext_bytes = batch_extent(batch, ext, ext, "sppark_lde_batch: extent overflows size_t");
+    const size_t aux_bytes = batch_extent(batch, dom, dom, "sppark_lde_batch: aux_out extent overflows size_t");
+    const gpu_info& gpu = select_gpu((int)device_id);
+    const bool dev = is_device_pointer(inout), aux_dev = aux_out && is_device_pointer(aux_out);
+    if (dev) check_device_extent(inout, ext_bytes, "sppark_lde_batch: inout extends past its allocation");
+    if (aux_dev) check_device_extent(aux_out, aux_bytes, "sppark_lde_batch: aux_out extends past its allocation");
+    // device scratch per column: [tmp: dom][aux: dom, when it has to be staged][ext, when inout is a host buffer]; whole
+    // columns per chunk, SPPARK_BATCH_CHUNK_BYTES at most (one column when a column needs more)
+    const size_t per_col = (dom + (aux_out && !aux_dev ? dom : 0) + (dev ? 0 : ext)) * sizeof(fr_t);
+    const size_t cols = std::min(batch, std::max<size_t>(1, BATCH_CHUNK_BYTES / per_col));
+    pooled_scratch buf(cols * per_col);
+    fr_t* d_tmp = (fr_t*)buf.p;
+    fr_t* d_stage_aux = d_tmp + cols * dom;
+    fr_t* d_stage_ext = d_stage_aux + (aux_out && !aux_dev ? cols * dom : 0);
+    auto& E = ntt_engine<fr_t>::instance();
+    for (size_t c0 = 0; c0 < batch; c0 += cols) {
+        const size_t k = std::min(cols, batch - c0);
+        fr_t* h_ext = (fr_t*)inout + c0 * ext;
+        fr_t* d_ext = dev ? h_ext : d_stage_ext;
+        fr_t* d_aux = aux_out ? (aux_dev ? (fr_t*)aux_out + c0 * dom : d_stage_aux) : nullptr;
+        if (!dev) HIP_OK(hipMemcpy2DAsync(d_ext, ext * sizeof(fr_t), h_ext, ext * sizeof(fr_t), dom * sizeof(fr_t), k, hipMemcpyHostToDevice, stream));
+        E.lde(gpu, d_ext, d_tmp, d_aux, lg_domain, lg_blowup, stream, k);
+        if (aux_out && !aux_dev) HIP_OK(hipMemcpyAsync((fr_t*)aux_out + c0 * dom, d_aux, k * dom * sizeof(fr_t), hipMemcpyDeviceToHost, stream));
+        if (!dev) HIP_OK(hipMemcpyAsync(h_ext, d_ext, k * ext * sizeof(fr_t), hipMemcpyDeviceToHost, stream));
+    }
+    HIP_OK(hipStreamSynchronize(stream));
+    buf.done();
+}
+
+SPPARK_FFI RustError sppark_ntt_batch(size_t device_id, void* inout, uint32_t lg_domain_size, size_t batch, size_t stride,
+                                      int ntt_order, int ntt_direction, int ntt_type, void* stream)
+{   return guarded([&] { ntt_batch_any(device_id, inout, lg_domain_size, batch, stride, ntt_order, ntt_direction, ntt_type, (hipStream_t)stream); });   }
+
+SPPARK_FFI RustError sppark_lde_batch(size_t device_id, void* inout, uint32_t lg_domain_size, uint32_t lg_blowup, size_t batch,
+                                      void* aux_out, void* stream)
+{   return guarded([&] { lde_batch_any(device_id, inout, lg_domain_size, lg_blowup, batch, aux_out, (hipStream_t)stream); });   }
+
+SPPARK_FFI size_t sppark_ntt_batch_launch_cols(size_t device_id, uint32_t lg_domain_size)
+{
+    if (lg_domain_size > fr_t::TWO_ADICITY) return 0;
+    try { return ntt_engine<fr_t>::instance().launch_cols(select_gpu((int)device_id), lg_domain_size); }
+    catch (...) { (void)hipGetLastError(); return 0; }
 }
 
 #include "poly_api.hpp"

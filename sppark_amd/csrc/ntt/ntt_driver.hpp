@@ -129,6 +129,17 @@ class ntt_engine {
         return dflt;
 #endif
     }
+    // batched transforms of up to this size run several columns per wave (k_ntt_small_packed, at most NTT_PACKED_MAX_LG = 6);
+    // above it one work-group per column.  Tuning builds: SPPARK_NTT_PACKED_MAX, 0 = never (DESIGN.md "Batched transforms")
+    static unsigned packed_max_lg()
+    {
+#ifdef SPPARK_TUNING
+        static const unsigned v = [] { const char* e = getenv("SPPARK_NTT_PACKED_MAX"); return e ? std::min((unsigned)atoi(e), NTT_PACKED_MAX_LG) : NTT_PACKED_MAX_LG; }();
+        return v;
+#else
+        return NTT_PACKED_MAX_LG;
+#endif
+    }
     // tuning builds: SPPARK_NTT_SMALL_SIZED=0 runs every size through the run-time-size instance
     static bool small_sized()
     {
@@ -247,12 +258,28 @@ public:
     // transform runs another plan the spread is launched here first.
     // |lde->out| instead (sppark_lde's inverse NR transform): the result goes to |out|, |d| is scratch afterwards -- the last step
     // of the radix-64 plan stores there (ntt_r64_args::out), any other plan runs in place and copies.
+    // |batch| columns (sppark_ntt_batch / sppark_lde_batch): column j at d + j * col_stride.  Every launch below takes one grid
+    // row per column (blockIdx.y; the packed kernel: one per work-group of columns) and the columns share the tables; lde->src
+    // and lde->out then hold the columns packed, 2^lde->lg_domain and 2^lg elements apart.  A batch above what one launch can
+    // index (launch_cols) runs as several launch chunks.
     struct lde_input { const F* src; unsigned lg_domain, lg_blowup; F* out; };
-    void run(const gpu_info& gpu, F* d, unsigned lg, int order, int direction, int type, hipStream_t stream, const lde_input* lde = nullptr)
+    void run(const gpu_info& gpu, F* d, unsigned lg, int order, int direction, int type, hipStream_t stream, const lde_input* lde = nullptr,
+             size_t batch = 1, size_t col_stride = 0)
     {
+        if (batch > 1) {
+            const size_t per = launch_cols(gpu, lg);
+            if (batch > per) {
+                for (size_t c0 = 0; c0 < batch; c0 += per) {
+                    lde_input sub{};
+                    if (lde) { sub = *lde; if (sub.src) sub.src += c0 << lde->lg_domain; if (sub.out) sub.out += c0 << lg; }
+                    run(gpu, d + c0 * col_stride, lg, order, direction, type, stream, lde ? &sub : nullptr, std::min(per, batch - c0), col_stride);
+                }
+                return;
+            }
+        }
         if (lg == 0) {                                              // ntt/ntt.cuh:220-221 (one element: the hand-over of sppark_lde still happens)
-            if (lde && lde->out) HIP_OK(hipMemcpyAsync(lde->out, d, sizeof(F), hipMemcpyDeviceToDevice, stream));
-            else if (lde) lde_spread(gpu, d, lde->src, lde->lg_domain, lde->lg_blowup, true, stream);
+            if (lde && lde->out) copy_cols(lde->out, 1, d, col_stride, 1, batch, stream);
+            else if (lde) lde_spread(gpu, d, lde->src, lde->lg_domain, lde->lg_blowup, true, stream, batch, col_stride, 1);
             return;
         }
         if (lg > F::TWO_ADICITY || order < 0 || order > 3) HIP_OK(hipErrorInvalidValue);
@@ -266,15 +293,37 @@ public:
         // in one launch (k_ntt_small, ntt_kernels.hpp)
         F* final_out = lde ? lde->out : nullptr;
         if (final_out) lde = nullptr;
-        if (lde && lg <= small_max_lg()) { lde_spread(gpu, d, lde->src, lde->lg_domain, lde->lg_blowup, true, stream); lde = nullptr; }
+        if (lde && lg <= small_max_lg()) {
+            lde_spread(gpu, d, lde->src, lde->lg_domain, lde->lg_blowup, true, stream, batch, col_stride, (size_t)1 << lde->lg_domain);
+            lde = nullptr;
+        }
+        if (lg <= small_max_lg() && batch > 1 && lg <= packed_max_lg()) {         // several columns per wave (k_ntt_small_packed)
+            const unsigned flags = ntt_small_flags(order, inverse != 0, type == NTT_COSET);
+            const unsigned groups = (unsigned)((batch + (256u >> (lg - 1)) - 1) >> (9 - lg));
+#define SPPARK_NTT_PACKED_PICK(LG) do { \
+                if (inverse) hipLaunchKernelGGL((k_ntt_small_packed<F, true, LG>), dim3(1, groups), dim3(256), 0, stream, d, T, G, flags, col_stride, batch); \
+                else         hipLaunchKernelGGL((k_ntt_small_packed<F, false, LG>), dim3(1, groups), dim3(256), 0, stream, d, T, G, flags, col_stride, batch); } while (0)
+            switch (lg) {
+                case 1: SPPARK_NTT_PACKED_PICK(1); break;
+                case 2: SPPARK_NTT_PACKED_PICK(2); break;
+                case 3: SPPARK_NTT_PACKED_PICK(3); break;
+                case 4: SPPARK_NTT_PACKED_PICK(4); break;
+                case 5: SPPARK_NTT_PACKED_PICK(5); break;
+                default: SPPARK_NTT_PACKED_PICK(6); break;
+            }
+#undef SPPARK_NTT_PACKED_PICK
+            HIP_OK(hipGetLastError());
+            if (final_out) copy_cols(final_out, n, d, col_stride, n, batch, stream);
+            return;
+        }
         if (lg <= small_max_lg()) {
             const unsigned flags = ntt_small_flags(order, inverse != 0, type == NTT_COSET);
             const unsigned lanes = (unsigned)std::max<size_t>(64, n / 2);
             const size_t lds = lanes > 64 ? 2 * (size_t)lanes * sizeof(F) : 0;        // the exchanges across waves (ntt_rx_regroup)
             // (single-word fields: the sizes 2^8 ... 2^11 have their own instance, compiled for that size)
 #define SPPARK_NTT_SMALL_PICK(LGC) do { \
-                if (inverse) hipLaunchKernelGGL((k_ntt_small<F, true, LGC>), dim3(1), dim3(lanes), lds, stream, d, T, G, flags); \
-                else         hipLaunchKernelGGL((k_ntt_small<F, false, LGC>), dim3(1), dim3(lanes), lds, stream, d, T, G, flags); } while (0)
+                if (inverse) hipLaunchKernelGGL((k_ntt_small<F, true, LGC>), dim3(1, (unsigned)batch), dim3(lanes), lds, stream, d, T, G, flags, col_stride); \
+                else         hipLaunchKernelGGL((k_ntt_small<F, false, LGC>), dim3(1, (unsigned)batch), dim3(lanes), lds, stream, d, T, G, flags, col_stride); } while (0)
             if constexpr (sizeof(F) <= 8) {
                 switch (small_sized() ? lg : 0u) {
                     case 8:  SPPARK_NTT_SMALL_PICK(8); break;
@@ -287,13 +336,13 @@ public:
                 SPPARK_NTT_SMALL_PICK(0);
 #undef SPPARK_NTT_SMALL_PICK
             HIP_OK(hipGetLastError());
-            if (final_out) HIP_OK(hipMemcpyAsync(final_out, d, n * sizeof(F), hipMemcpyDeviceToDevice, stream));
+            if (final_out) copy_cols(final_out, n, d, col_stride, n, batch, stream);
             return;
         }
 
         bool bitrev, gs;
         switch (order) {
-            case NTT_NN: bit_reverse(d, lg, stream);
+            case NTT_NN: bit_reverse(d, lg, stream, batch, col_stride);
                          bitrev = true;  gs = false; break;
             case NTT_NR: bitrev = false; gs = true;  break;
             case NTT_RN: bitrev = true;  gs = false; break;
@@ -370,10 +419,11 @@ public:
             if constexpr (R64)
                 lde_fused = rp.nsteps && !gs && !inverse && order == NTT_RN && type == NTT_STANDARD && rp.step[rp.nsteps - 1].kind == 2
                          && lde->lg_blowup >= 1 && lde->lg_blowup <= 3 && lde->lg_domain + lde->lg_blowup == lg;
-            if (!lde_fused) lde_spread(gpu, d, lde->src, lde->lg_domain, lde->lg_blowup, true, stream);
+            if (!lde_fused) lde_spread(gpu, d, lde->src, lde->lg_domain, lde->lg_blowup, true, stream, batch, col_stride, (size_t)1 << lde->lg_domain);
         }
+        const unsigned ncol = (unsigned)batch;                     // (<= launch_cols: the grid's y dimension)
         if (!inverse && type == NTT_COSET && !cmode)
-            hipLaunchKernelGGL(k_coset<F>, dim3(egrid), dim3(256), 0, stream, d, G, (int)bitrev);
+            hipLaunchKernelGGL(k_coset<F>, dim3(egrid, ncol), dim3(256), 0, stream, d, G, (int)bitrev, col_stride);
         const bool lat = !R64 && knobs.lat_smax != 0;
         if (rp.nsteps) pl.npass = rp.nsteps;
         else if (lat)  pl = make_ntt_lat_plan(lg, knobs.lat_smax, knobs.lat_lgc, knobs.lat_lgt);
@@ -402,17 +452,17 @@ public:
                         const size_t lds = sizeof(F) << 12;
 #define SPPARK_R64_LAUNCH(K)                                                                                   \
                         do {                                                                                   \
-                            if (gs) { if (inverse) hipLaunchKernelGGL((K<F, true, true>), dim3(tiles), dim3(512), lds, stream, d, A);    \
-                                      else         hipLaunchKernelGGL((K<F, true, false>), dim3(tiles), dim3(512), lds, stream, d, A); } \
-                            else    { if (inverse) hipLaunchKernelGGL((K<F, false, true>), dim3(tiles), dim3(512), lds, stream, d, A);   \
-                                      else         hipLaunchKernelGGL((K<F, false, false>), dim3(tiles), dim3(512), lds, stream, d, A); } \
+                            if (gs) { if (inverse) hipLaunchKernelGGL((K<F, true, true>), dim3(tiles, ncol), dim3(512), lds, stream, d, A, col_stride);    \
+                                      else         hipLaunchKernelGGL((K<F, true, false>), dim3(tiles, ncol), dim3(512), lds, stream, d, A, col_stride); } \
+                            else    { if (inverse) hipLaunchKernelGGL((K<F, false, true>), dim3(tiles, ncol), dim3(512), lds, stream, d, A, col_stride);   \
+                                      else         hipLaunchKernelGGL((K<F, false, false>), dim3(tiles, ncol), dim3(512), lds, stream, d, A, col_stride); } \
                         } while (0)
-                        if (final_out && last && st.kind == 2 && gs) { A.out = final_out; final_out = nullptr; }
+                        if (final_out && last && st.kind == 2 && gs) { A.out = final_out; A.aux_stride = n; final_out = nullptr; }
                         if (lde_fused && i == 0) {
                             const table_set tg = tables(gpu.hip_id, lde->lg_domain, 0, stream);
                             A.lde_src = lde->src; A.lde_glo = tg.glo; A.lde_ghi = tg.ghi; A.lde_gh = tg.h;
-                            A.lde_lgd = lde->lg_domain; A.lde_lgb = lde->lg_blowup;
-                            hipLaunchKernelGGL((k_ntt12<F, false, false, true>), dim3(tiles), dim3(512), lds, stream, d, A);
+                            A.lde_lgd = lde->lg_domain; A.lde_lgb = lde->lg_blowup; A.aux_stride = (size_t)1 << lde->lg_domain;
+                            hipLaunchKernelGGL((k_ntt12<F, false, false, true>), dim3(tiles, ncol), dim3(512), lds, stream, d, A, col_stride);
                         } else if (st.kind == 1) SPPARK_R64_LAUNCH(k_ntt6); else SPPARK_R64_LAUNCH(k_ntt12);
 #undef SPPARK_R64_LAUNCH
                         continue;
@@ -439,10 +489,10 @@ public:
                     const unsigned lanes = (unsigned)std::min<size_t>(std::max<size_t>(tile_elems / 2, 64), 1024);
                     const size_t lat_lds = tile_elems * sizeof(F);
                     if (lat_lds > 64 * 1024) HIP_OK(hipErrorInvalidValue);      // (only a tuning build can ask for such a tile)
-                    if (gs) { if (inverse) hipLaunchKernelGGL((k_ntt_pass_lat<F, true, true>), dim3(tiles), dim3(lanes), lat_lds, stream, d, T, P);
-                              else         hipLaunchKernelGGL((k_ntt_pass_lat<F, true, false>), dim3(tiles), dim3(lanes), lat_lds, stream, d, T, P); }
-                    else    { if (inverse) hipLaunchKernelGGL((k_ntt_pass_lat<F, false, true>), dim3(tiles), dim3(lanes), lat_lds, stream, d, T, P);
-                              else         hipLaunchKernelGGL((k_ntt_pass_lat<F, false, false>), dim3(tiles), dim3(lanes), lat_lds, stream, d, T, P); }
+                    if (gs) { if (inverse) hipLaunchKernelGGL((k_ntt_pass_lat<F, true, true>), dim3(tiles, ncol), dim3(lanes), lat_lds, stream, d, T, P, col_stride);
+                              else         hipLaunchKernelGGL((k_ntt_pass_lat<F, true, false>), dim3(tiles, ncol), dim3(lanes), lat_lds, stream, d, T, P, col_stride); }
+                    else    { if (inverse) hipLaunchKernelGGL((k_ntt_pass_lat<F, false, true>), dim3(tiles, ncol), dim3(lanes), lat_lds, stream, d, T, P, col_stride);
+                              else         hipLaunchKernelGGL((k_ntt_pass_lat<F, false, false>), dim3(tiles, ncol), dim3(lanes), lat_lds, stream, d, T, P, col_stride); }
                     continue;
                 }
             }
@@ -458,40 +508,53 @@ public:
                                         : (inverse ? (const void*)k_ntt_pass<F, false, true, R1, R2> : (const void*)k_ntt_pass<F, false, false, R1, R2>); \
                     HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));     \
                 }                                                                                              \
-                if (gs) { if (inverse) hipLaunchKernelGGL((k_ntt_pass<F, true, true, R1, R2>), dim3(tiles), dim3(nthr), lds, stream, d, T, P);   \
-                          else         hipLaunchKernelGGL((k_ntt_pass<F, true, false, R1, R2>), dim3(tiles), dim3(nthr), lds, stream, d, T, P); } \
-                else    { if (inverse) hipLaunchKernelGGL((k_ntt_pass<F, false, true, R1, R2>), dim3(tiles), dim3(nthr), lds, stream, d, T, P);  \
-                          else         hipLaunchKernelGGL((k_ntt_pass<F, false, false, R1, R2>), dim3(tiles), dim3(nthr), lds, stream, d, T, P); } \
+                if (gs) { if (inverse) hipLaunchKernelGGL((k_ntt_pass<F, true, true, R1, R2>), dim3(tiles, ncol), dim3(nthr), lds, stream, d, T, P, col_stride);   \
+                          else         hipLaunchKernelGGL((k_ntt_pass<F, true, false, R1, R2>), dim3(tiles, ncol), dim3(nthr), lds, stream, d, T, P, col_stride); } \
+                else    { if (inverse) hipLaunchKernelGGL((k_ntt_pass<F, false, true, R1, R2>), dim3(tiles, ncol), dim3(nthr), lds, stream, d, T, P, col_stride);  \
+                          else         hipLaunchKernelGGL((k_ntt_pass<F, false, false, R1, R2>), dim3(tiles, ncol), dim3(nthr), lds, stream, d, T, P, col_stride); } \
             } while (0)
             if constexpr (S_MAX >= 8) { SPPARK_NTT_DISPATCH_S(P.S, SPPARK_NTT_LAUNCH); }
             else                      { SPPARK_NTT_DISPATCH_S4(P.S, SPPARK_NTT_LAUNCH); }
 #undef SPPARK_NTT_LAUNCH
         }
         if (inverse && type == NTT_COSET && !cmode)
-            hipLaunchKernelGGL(k_coset<F>, dim3(egrid), dim3(256), 0, stream, d, G, (int)!bitrev);
+            hipLaunchKernelGGL(k_coset<F>, dim3(egrid, ncol), dim3(256), 0, stream, d, G, (int)!bitrev, col_stride);
         if (order == NTT_RR)
-            bit_reverse(d, lg, stream);
+            bit_reverse(d, lg, stream, batch, col_stride);
         HIP_OK(hipGetLastError());
-        if (final_out) HIP_OK(hipMemcpyAsync(final_out, d, n * sizeof(F), hipMemcpyDeviceToDevice, stream));      // (no step stored there)
+        if (final_out) copy_cols(final_out, n, d, col_stride, n, batch, stream);      // (no step stored there)
+    }
+
+    // columns one launch of run() covers: the grid's y dimension, times the columns of a work-group of k_ntt_small_packed
+    size_t launch_cols(const gpu_info& gpu, unsigned lg)
+    {
+        const size_t rows = (size_t)std::max(gpu.prop.maxGridSize[1], 1);
+        return lg >= 1 && lg <= packed_max_lg() && lg <= small_max_lg() ? rows << (9 - lg) : rows;
+    }
+    // |batch| columns of |n| elements from src (src_stride apart) to dst (dst_stride apart), device to device
+    static void copy_cols(F* dst, size_t dst_stride, const F* src, size_t src_stride, size_t n, size_t batch, hipStream_t stream)
+    {
+        if (batch == 1) HIP_OK(hipMemcpyAsync(dst, src, n * sizeof(F), hipMemcpyDeviceToDevice, stream));
+        else HIP_OK(hipMemcpy2DAsync(dst, dst_stride * sizeof(F), src, src_stride * sizeof(F), n * sizeof(F), batch, hipMemcpyDeviceToDevice, stream));
     }
 
     // in-place bit-reversal permutation (NN and RR orders; ntt/ntt.cuh:44-79)
-    static void bit_reverse(F* d, unsigned lg, hipStream_t stream)
+    static void bit_reverse(F* d, unsigned lg, hipStream_t stream, size_t batch = 1, size_t col_stride = 0)
     {
         constexpr unsigned TB = bitrev_tile_bits<F>::value;
         const size_t n = (size_t)1 << lg;
         if (lg >= 2 * TB + 1) {
             size_t lds = 2 * (((size_t)(1u << TB) + 1) << TB) * sizeof(F);
             // 16-byte accesses for the single-word fields (any 16-byte aligned buffer; a view at an odd element offset
-            // takes the element-wise tiles)
+            // takes the element-wise tiles) -- in a batch, only when every column starts 16-byte aligned
             bool vec = false;
-            if constexpr (sizeof(F) <= 8) vec = ((uintptr_t)d & 15) == 0;
+            if constexpr (sizeof(F) <= 8) vec = ((uintptr_t)d & 15) == 0 && (batch == 1 || ((col_stride * sizeof(F)) & 15) == 0);
             if constexpr (sizeof(F) <= 8) {
-                if (vec) hipLaunchKernelGGL((k_bitrev_tiled_vec<F, TB>), dim3((unsigned)(n >> (2 * TB))), dim3(256), lds, stream, d, lg);
+                if (vec) hipLaunchKernelGGL((k_bitrev_tiled_vec<F, TB>), dim3((unsigned)(n >> (2 * TB)), (unsigned)batch), dim3(256), lds, stream, d, lg, col_stride);
             }
-            if (!vec) hipLaunchKernelGGL((k_bitrev_tiled<F, TB>), dim3((unsigned)(n >> (2 * TB))), dim3(256), lds, stream, d, lg);
+            if (!vec) hipLaunchKernelGGL((k_bitrev_tiled<F, TB>), dim3((unsigned)(n >> (2 * TB)), (unsigned)batch), dim3(256), lds, stream, d, lg, col_stride);
         } else {
-            hipLaunchKernelGGL(k_bitrev<F>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d, lg);
+            hipLaunchKernelGGL(k_bitrev<F>, dim3((unsigned)((n + 255) / 256), (unsigned)batch), dim3(256), 0, stream, d, lg, col_stride);
         }
     }
 
@@ -502,7 +565,7 @@ public:
         const table_set ts = tables(gpu.hip_id, lg, 0, stream);
         ntt_tables<F> G{ts.glo, ts.ghi, nullptr, lg, ts.h, ts.scale, nullptr};
         const size_t n = (size_t)1 << lg;
-        hipLaunchKernelGGL(k_coset<F>, dim3((unsigned)std::min<size_t>((n + 255) / 256, (size_t)1 << 22)), dim3(256), 0, stream, d, G, 1);
+        hipLaunchKernelGGL(k_coset<F>, dim3((unsigned)std::min<size_t>((n + 255) / 256, (size_t)1 << 22)), dim3(256), 0, stream, d, G, 1, (size_t)0);
         HIP_OK(hipGetLastError());
     }
 
@@ -515,8 +578,9 @@ public:
     // as long as P(lo) >= hi: hi = ext - (ext - lo) / blowup.  The ranges shrink geometrically
     // ([0, ext - dom), then dom (1 - 1/blowup) elements, ...): 2 + lg_domain / lg_blowup launches, kernel
     // boundaries instead of the reference's cooperative grid sync (kernels.cu:199-200).
+    // |batch| > 1 (run() within the batched LDE): separate buffers, the columns out_stride / in_stride elements apart
     void lde_spread(const gpu_info& gpu, F* d_out, const F* d_in, unsigned lg_domain, unsigned lg_blowup,
-                    bool shift, hipStream_t stream)
+                    bool shift, hipStream_t stream, size_t batch = 1, size_t out_stride = 0, size_t in_stride = 0)
     {
         if (lg_domain + lg_blowup > F::TWO_ADICITY) HIP_OK(hipErrorInvalidValue);
         const size_t dom = (size_t)1 << lg_domain, ext = dom << lg_blowup;
@@ -524,11 +588,17 @@ public:
         if (overlap && (lg_blowup == 0 || d_in != d_out + (ext - dom))) HIP_OK(hipErrorInvalidValue);
         const table_set ts = tables(gpu.hip_id, lg_domain, 0, stream);
         ntt_tables<F> G{ts.glo, ts.ghi, nullptr, lg_domain, ts.h, ts.scale, nullptr};
-        for (size_t lo = 0; lo < ext;) {
-            const size_t hi = overlap ? ext - ((ext - lo) >> lg_blowup) : ext;
-            hipLaunchKernelGGL(k_lde_spread<F>, dim3((unsigned)((hi - lo + 255) / 256)), dim3(256), 0, stream,
-                               d_out, d_in, G, lg_domain, lg_blowup, (int)shift, lo, hi);
-            lo = hi;
+        // (a grid row per column: more columns than the grid's y dimension -- the packed sizes' launch chunks hold up to
+        //  256 / (n/2) times as many -- take several launches)
+        const size_t rows = (size_t)std::max(gpu.prop.maxGridSize[1], 1);
+        for (size_t c0 = 0; c0 < batch; c0 += rows) {
+            const unsigned ncol = (unsigned)std::min(rows, batch - c0);
+            for (size_t lo = 0; lo < ext;) {
+                const size_t hi = overlap ? ext - ((ext - lo) >> lg_blowup) : ext;
+                hipLaunchKernelGGL(k_lde_spread<F>, dim3((unsigned)((hi - lo + 255) / 256), ncol), dim3(256), 0, stream,
+                                   d_out + c0 * out_stride, d_in + c0 * in_stride, G, lg_domain, lg_blowup, (int)shift, lo, hi, out_stride, in_stride);
+                lo = hi;
+            }
         }
         HIP_OK(hipGetLastError());
     }
@@ -537,22 +607,26 @@ public:
     // iNTT(NR) of the 2^lg_domain evaluations in d_ext[0 .. 2^lg_domain), coset shift +
     // zero-extension in bit-reversed order, forward NTT(RN) of size 2^(lg_domain+lg_blowup).
     // d_tmp: 2^lg_domain scratch elements; d_aux (nullable): the coefficients, natural order.
-    void lde(const gpu_info& gpu, F* d_ext, F* d_tmp, F* d_aux, unsigned lg_domain, unsigned lg_blowup, hipStream_t stream)
+    // |batch| columns (sppark_lde_batch): d_ext's 2^(lg_domain + lg_blowup) elements apart, d_tmp's and d_aux's packed.
+    void lde(const gpu_info& gpu, F* d_ext, F* d_tmp, F* d_aux, unsigned lg_domain, unsigned lg_blowup, hipStream_t stream, size_t batch = 1)
     {
         if (lg_domain + lg_blowup > F::TWO_ADICITY) HIP_OK(hipErrorInvalidValue);
-        const size_t dom = (size_t)1 << lg_domain;
+        const size_t dom = (size_t)1 << lg_domain, ext = dom << lg_blowup;
         // (the inverse transform runs in the first 2^lg_domain elements of d_ext -- overwritten below anyway -- and leaves the
         //  coefficients in d_tmp: its last step stores there, no copy in front of it)
         const lde_input lo{nullptr, 0, 0, d_tmp};
-        run(gpu, d_ext, lg_domain, NTT_NR, NTT_INVERSE, NTT_STANDARD, stream, &lo);
+        run(gpu, d_ext, lg_domain, NTT_NR, NTT_INVERSE, NTT_STANDARD, stream, &lo, batch, ext);
         if (d_aux) {
-            hipLaunchKernelGGL(k_bitrev_copy<F>, dim3((unsigned)((dom + 255) / 256)), dim3(256), 0, stream, d_aux, d_tmp, lg_domain);
+            const size_t rows = (size_t)std::max(gpu.prop.maxGridSize[1], 1);
+            for (size_t c0 = 0; c0 < batch; c0 += rows)
+                hipLaunchKernelGGL(k_bitrev_copy<F>, dim3((unsigned)((dom + 255) / 256), (unsigned)std::min(rows, batch - c0)), dim3(256), 0, stream,
+                                   d_aux + c0 * dom, d_tmp + c0 * dom, lg_domain, dom);
             HIP_OK(hipGetLastError());
         }
         // (the spread + coset shift of LDE_launch ride in the forward transform's first step where the plan allows: 134 MB
         //  never written and a launch less at 2^22 -> 2^24)
         const lde_input li{d_tmp, lg_domain, lg_blowup, nullptr};
-        run(gpu, d_ext, lg_domain + lg_blowup, NTT_RN, NTT_FORWARD, NTT_STANDARD, stream, &li);
+        run(gpu, d_ext, lg_domain + lg_blowup, NTT_RN, NTT_FORWARD, NTT_STANDARD, stream, &li, batch, ext);
     }
 };
 

@@ -319,8 +319,9 @@ template<class F, bool DIF, bool INV, unsigned R1, unsigned R2>
 // 32 KB tiles per CU -- changes nothing: 0.264 vs 0.263 ms at 2^24, tools/gpu_r2_job14.sh; the pass is
 // bound by its instruction count.)
 __global__ __launch_bounds__(512)
-void k_ntt_pass(F* data, ntt_tables<F> T, ntt_pass P)
+void k_ntt_pass(F* data, ntt_tables<F> T, ntt_pass P, size_t col_stride)
 {
+    data += (size_t)blockIdx.y * col_stride;                       // (batched transforms: one column per grid row)
     extern __shared__ unsigned char ntt_lds[];
     F* tile = reinterpret_cast<F*>(ntt_lds);
     const unsigned tid = threadIdx.x, nt = blockDim.x;
@@ -442,8 +443,9 @@ SPPARK_DEVFN void ntt_lat_store(F* data, const F* tile, const ntt_tables<F>& T, 
 // costs more than the 0.375 products per element it saves.  Removed.
 template<class F, bool DIF, bool INV>
 __global__ __launch_bounds__(1024)
-void k_ntt_pass_lat(F* data, ntt_tables<F> T, ntt_pass P)
+void k_ntt_pass_lat(F* data, ntt_tables<F> T, ntt_pass P, size_t col_stride)
 {
+    data += (size_t)blockIdx.y * col_stride;
     extern __shared__ unsigned char ntt_lds[];
     F* tile = reinterpret_cast<F*>(ntt_lds);
     const unsigned tid = threadIdx.x, nt = blockDim.x;
@@ -567,17 +569,20 @@ SPPARK_DEVFN void ntt_rx_regroup(F& x0, F& x1, const F& sum, const F& dif, unsig
 // LGC: the size the body is compiled for (0: any size up to the cap, read from the tables at run time).  With the size
 // known, the stages are one straight line -- no per-stage branch, no select between the top twiddle and the others, and
 // each stage waits for ITS twiddle instead of all the loads.
-template<class F, bool INV, bool GS, unsigned LGC = 0>
+// PACKED (k_ntt_small_packed): lane l carries pair l mod n/2 of the column its segment of n/2 lanes holds, |col_live| is false
+// past the batch's last column (such lanes run the exchanges and touch no memory).
+template<class F, bool INV, bool GS, unsigned LGC = 0, bool PACKED = false>
 SPPARK_DEVFN void ntt_rx_run(F* data, F* lds, const ntt_tables<F>& T, const ntt_tables<F>& G, unsigned flags,
-                             unsigned l, unsigned lanes)
+                             unsigned l, unsigned lanes, bool col_live = true)
 {
     constexpr unsigned MAXLG = ntt_small_cap<F>::value;
-    static_assert(LGC <= MAXLG && (LGC == 0 || LGC >= 7), "a compiled-in size fills at least one wave");
+    static_assert(LGC <= MAXLG && (PACKED ? LGC >= 1 && LGC <= 6 : LGC == 0 || LGC >= 7),
+                  "a compiled-in size fills at least one wave; packed columns stay inside one");
     // (a one-element "transform" has no pair: every lane idle, nothing read or written -- the driver returns before it gets
     // here, ntt_engine::run, but the kernel is safe on its own)
     const unsigned lg = LGC ? LGC : T.lg_n, nh = lg ? 1u << (lg - 1) : 0u;
-    const bool live = l < nh;
-    const unsigned lq = live ? l : 0;                           // (idle lanes read the tables at valid indices)
+    const bool live = PACKED ? col_live : l < nh;
+    const unsigned lq = PACKED ? (l & (nh - 1)) : live ? l : 0; // (idle lanes read the tables at valid indices)
     F x0 = F(), x1 = F(), sum, dif, g0 = F(), g1 = F(), w[MAXLG];
     // ---- every load of the transform, issued together ------------------------------------------------------------------
     // positions of the pair in the working array: GS (l, l + n/2) -> (2l, 2l + 1); CT (2l, 2l + 1) -> (l, l + n/2)
@@ -636,8 +641,9 @@ SPPARK_DEVFN void ntt_rx_run(F* data, F* lds, const ntt_tables<F>& T, const ntt_
 }
 template<class F, bool INV, unsigned LGC = 0>
 __global__ __launch_bounds__(1u << ((LGC ? LGC : ntt_small_cap<F>::value) - 1))
-void k_ntt_small(F* data, ntt_tables<F> T, ntt_tables<F> G, unsigned flags)
+void k_ntt_small(F* data, ntt_tables<F> T, ntt_tables<F> G, unsigned flags, size_t col_stride)
 {
+    data += (size_t)blockIdx.y * col_stride;
     extern __shared__ unsigned char ntt_lds[];
     F* lds = reinterpret_cast<F*>(ntt_lds);
     if (flags & NTT_SMALL_GS) ntt_rx_run<F, INV, true, LGC>(data, lds, T, G, flags, threadIdx.x, blockDim.x);    // (uniform over the launch)
@@ -648,6 +654,34 @@ void k_ntt_small(F* data, ntt_tables<F> T, ntt_tables<F> G, unsigned flags)
 #define SPPARK_NTT_SMALL_ALL_NARROW(X) X(false, 0) X(false, 8) X(false, 9) X(false, 10) X(false, 11) \
                                        X(true, 0) X(true, 8) X(true, 9) X(true, 10) X(true, 11)
 #define SPPARK_NTT_SMALL_ALL_WIDE(X)   X(false, 0) X(true, 0)
+
+// ---- batches of tiny transforms: several columns per wave (sppark_ntt_batch) -------------------------------------------
+// k_ntt_small gives each column max(64, n/2) lanes: at 2^6 half of every wave idles, at 2^1 ... 2^3 nearly all of it -- sizes
+// that only occur in batches.  Here a work-group of 256 lanes carries 256 / (n/2) columns, one segment of n/2 consecutive
+// lanes each, and every segment runs ntt_rx_run on its column.  The exchanges of a 2^lg transform are at distances 2^d <
+// n/2 = 2^(lg-1) <= 32, so they stay inside the segment: permlane16_swap, DPP moves and ds_bpermute on the hardware lane,
+// no LDS, no barrier.  Instances per size (LG = 1 ... 6) and direction: a straight line of lg stages.
+// The column of a lane: group * (256 / (n/2)) + tid / (n/2), group = blockIdx.y; |ncols| columns in this launch.  One lane's
+// work as a function of (group, tid) so that the host emulation (tests/emu/emu_ntt_batch.cpp) runs this very code; |lds|: the
+// emulation's exchange buffers (the device never touches it at these sizes).
+template<class F, bool INV, unsigned LG>
+SPPARK_DEVFN void ntt_packed_lane(F* data, F* lds, const ntt_tables<F>& T, const ntt_tables<F>& G, unsigned flags,
+                                  size_t col_stride, size_t ncols, size_t group, unsigned tid)
+{
+    constexpr unsigned NH = 1u << (LG - 1);
+    const size_t col = group * (256u / NH) + tid / NH;
+    const bool live = col < ncols;
+    F* d = data + (live ? col : 0) * col_stride;
+    if (flags & NTT_SMALL_GS) ntt_rx_run<F, INV, true, LG, true>(d, lds, T, G, flags, tid, 256u, live);
+    else                      ntt_rx_run<F, INV, false, LG, true>(d, lds, T, G, flags, tid, 256u, live);
+}
+template<class F, bool INV, unsigned LG>
+__global__ __launch_bounds__(256)
+void k_ntt_small_packed(F* data, ntt_tables<F> T, ntt_tables<F> G, unsigned flags, size_t col_stride, size_t ncols)
+{   ntt_packed_lane<F, INV, LG>(data, nullptr, T, G, flags, col_stride, ncols, blockIdx.y, threadIdx.x);   }
+static constexpr unsigned NTT_PACKED_MAX_LG = 6;
+#define SPPARK_NTT_PACKED_ALL(X) X(false, 1) X(false, 2) X(false, 3) X(false, 4) X(false, 5) X(false, 6) \
+                                 X(true, 1) X(true, 2) X(true, 3) X(true, 4) X(true, 5) X(true, 6)
 // the flags of an (order, direction, type) call -- ntt/ntt.cuh:174-209: NN = bit_rev + CT, NR = GS, RN = CT, RR = GS + bit_rev
 static inline unsigned ntt_small_flags(int order, bool inverse, bool coset)
 {
@@ -695,8 +729,9 @@ SPPARK_DEVFN void bitrev_item(F* data, unsigned lg_n, size_t i)
     if (i < r) { F t = data[i]; data[i] = data[r]; data[r] = t; }
 }
 template<class F>
-__global__ __launch_bounds__(256) void k_bitrev(F* data, unsigned lg_n)
+__global__ __launch_bounds__(256) void k_bitrev(F* data, unsigned lg_n, size_t col_stride)
 {
+    data += (size_t)blockIdx.y * col_stride;
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < ((size_t)1 << lg_n)) bitrev_item(data, lg_n, i);
 }
@@ -735,8 +770,9 @@ SPPARK_DEVFN void bitrev_tile_item(F* data, F* ldsA, F* ldsB, unsigned lg_n, siz
     }
 }
 template<class F, unsigned TB>
-__global__ __launch_bounds__(256) void k_bitrev_tiled(F* data, unsigned lg_n)
+__global__ __launch_bounds__(256) void k_bitrev_tiled(F* data, unsigned lg_n, size_t col_stride)
 {
+    data += (size_t)blockIdx.y * col_stride;
     extern __shared__ unsigned char bitrev_lds[];
     F* ldsA = reinterpret_cast<F*>(bitrev_lds);
     F* ldsB = ldsA + (((1u << TB) + 1) << TB);
@@ -796,8 +832,9 @@ SPPARK_DEVFN void bitrev_tile_vec_item(F* data, F* ldsA, F* ldsB, unsigned lg_n,
     }
 }
 template<class F, unsigned TB>
-__global__ __launch_bounds__(256) void k_bitrev_tiled_vec(F* data, unsigned lg_n)
+__global__ __launch_bounds__(256) void k_bitrev_tiled_vec(F* data, unsigned lg_n, size_t col_stride)
 {
+    data += (size_t)blockIdx.y * col_stride;                       // (every column 16-byte aligned: the driver checks)
     extern __shared__ unsigned char bitrev_lds[];
     F* ldsA = reinterpret_cast<F*>(bitrev_lds);
     F* ldsB = ldsA + (((1u << TB) + 1) << TB);
@@ -817,8 +854,9 @@ SPPARK_DEVFN void coset_item(F* data, const ntt_tables<F>& G, int bitrev, size_t
     data[i] = data[i] * ntt_twiddle(G, e);
 }
 template<class F>
-__global__ __launch_bounds__(256) void k_coset(F* data, ntt_tables<F> G, int bitrev)
+__global__ __launch_bounds__(256) void k_coset(F* data, ntt_tables<F> G, int bitrev, size_t col_stride)
 {
+    data += (size_t)blockIdx.y * col_stride;
     // grid-stride: a launch covers at most 2^32 - 1 work items, so 2^32 elements take a smaller grid (ntt_driver.hpp egrid)
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < ((size_t)1 << G.lg_n); i += (size_t)gridDim.x * blockDim.x)
         coset_item(data, G, bitrev, i);
@@ -851,15 +889,17 @@ SPPARK_DEVFN void lde_spread_item(F* out, const F* in, const ntt_tables<F>& G, u
 template<class F>
 __global__ __launch_bounds__(256)
 void k_lde_spread(F* out, const F* in, ntt_tables<F> G, unsigned lg_domain, unsigned lg_blowup, int shift,
-                  size_t o_begin, size_t o_end)
+                  size_t o_begin, size_t o_end, size_t out_stride, size_t in_stride)
 {
+    out += (size_t)blockIdx.y * out_stride; in += (size_t)blockIdx.y * in_stride;
     size_t o = o_begin + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (o < o_end) lde_spread_item(out, in, G, lg_domain, lg_blowup, shift, o);
 }
 // out[rev(i)] = in[i]  (out-of-place bit reversal: the aux output of LDE_aux, ntt/ntt.cuh:312-315)
 template<class F>
-__global__ __launch_bounds__(256) void k_bitrev_copy(F* out, const F* in, unsigned lg_n)
+__global__ __launch_bounds__(256) void k_bitrev_copy(F* out, const F* in, unsigned lg_n, size_t col_stride)
 {
+    out += (size_t)blockIdx.y * col_stride; in += (size_t)blockIdx.y * col_stride;
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= ((size_t)1 << lg_n)) return;
     size_t r = 0;

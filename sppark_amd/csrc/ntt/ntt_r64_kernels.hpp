@@ -57,6 +57,7 @@ template<class F> struct ntt_r64_args {
     const F* lde_src = nullptr;
     const F* lde_glo = nullptr; const F* lde_ghi = nullptr;     // the powers of g: ntt_tables lo / hi / h of the domain's size
     unsigned lde_gh = 0, lde_lgd = 0, lde_lgb = 0;
+    size_t aux_stride = 0;  // batched transforms: the column stride of |out| / |lde_src| (elements)
 };
 
 SPPARK_DEVFN unsigned wave_uniform(unsigned v)
@@ -174,8 +175,9 @@ SPPARK_DEVFN void ntt6_low(F* data, F* tile, const ntt_r64_args<F>& A, size_t ti
 
 template<class F, bool DIF, bool INV>
 __global__ __launch_bounds__(512)
-void k_ntt6(F* data, ntt_r64_args<F> A)
+void k_ntt6(F* data, ntt_r64_args<F> A, size_t col_stride)
 {
+    data += (size_t)blockIdx.y * col_stride;                       // (batched transforms: one column per grid row)
     extern __shared__ unsigned char ntt_lds[];
     F* tile = reinterpret_cast<F*>(ntt_lds);
     if (DIF) {
@@ -293,11 +295,13 @@ SPPARK_DEVFN void ntt12_round(F* sub, F* tile, const ntt_r64_args<F>& A, unsigne
 
 template<class F, bool DIF, bool INV, bool LDE = false>
 __global__ __launch_bounds__(512)
-void k_ntt12(F* data, ntt_r64_args<F> A)
+void k_ntt12(F* data, ntt_r64_args<F> A, size_t col_stride)
 {
     extern __shared__ unsigned char ntt_lds[];
     F* tile = reinterpret_cast<F*>(ntt_lds);
-    F* sub = data + ((size_t)blockIdx.x << 12);
+    F* sub = data + (size_t)blockIdx.y * col_stride + ((size_t)blockIdx.x << 12);
+    if (LDE) A.lde_src += (size_t)blockIdx.y * A.aux_stride;       // (the columns of lde_src / out: packed, aux_stride apart)
+    else if (DIF && A.out) A.out += (size_t)blockIdx.y * A.aux_stride;
     const unsigned lane = threadIdx.x;
     if (LDE) {                                                      // (forward DIT only: the driver's sppark_lde path)
         ntt12_round<F, false, INV, R12_B2, true>(sub, tile, A, lane, blockIdx.x); __syncthreads();

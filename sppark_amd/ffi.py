@@ -164,6 +164,12 @@ def load(name):
         L.sppark_ntt_cached_scratch_bytes.restype = sz
         L.sppark_ntt_cached_tables.argtypes = []
         L.sppark_ntt_cached_tables.restype = sz
+        L.sppark_ntt_batch.argtypes = [sz, vp, u32, sz, sz, ci, ci, ci, vp]       # include/sppark_amd_batch.h
+        L.sppark_ntt_batch.restype = _Error
+        L.sppark_lde_batch.argtypes = [sz, vp, u32, u32, sz, vp, vp]
+        L.sppark_lde_batch.restype = _Error
+        L.sppark_ntt_batch_launch_cols.argtypes = [sz, u32]
+        L.sppark_ntt_batch_launch_cols.restype = sz
 
     if name in NTT_FIELDS or name in CURVES or name in POLY_ONLY:
         L.sppark_prefix_op.argtypes = [sz, vp, vp, sz, ci, vp]

@@ -102,3 +102,61 @@ def LDE_expand(device_id, d_out, d_in, lg_domain_size, lg_blowup, field="gl64", 
     pi, _k2 = ffi.as_pointer(d_in)
     ffi.check(L, L.sppark_lde_expand(device_id, po, pi, lg_domain_size, lg_blowup, stream))
     return d_out
+
+
+# ---- batched transforms (include/sppark_amd_batch.h) ----
+def _rows(x, field, what):
+    """(address, keepalive, rows, field elements per row, row stride in field elements) of a 2-D numpy array or torch tensor
+    holding one polynomial per row; the elements of a row must be adjacent"""
+    if field not in _ELEM_BYTES:
+        raise ValueError("no NTT over %r" % (field,))
+    if len(tuple(x.shape)) != 2:
+        raise ValueError("%s must be 2-D: one polynomial per row" % what)
+    rows, cols = (int(v) for v in x.shape)
+    if hasattr(x, "data_ptr"):                      # torch tensor: strides in elements of its dtype
+        item = x.element_size()
+        st = [int(v) * item for v in x.stride()]
+        ptr = x.data_ptr()
+    else:                                           # numpy: strides in bytes
+        item = x.itemsize
+        st = [int(v) for v in x.strides]
+        ptr = x.ctypes.data
+    eb = _ELEM_BYTES[field]
+    if (cols * item) % eb:
+        raise ValueError("%s: a row must hold whole field elements (%d bytes each)" % (what, eb))
+    n = cols * item // eb
+    if cols > 1 and st[1] != item:
+        raise ValueError("%s: the inner stride must be 1" % what)
+    row = st[0] if rows > 1 else n * eb
+    if row < n * eb or row % eb:
+        raise ValueError("%s: rows must not overlap and must start on a field element" % what)
+    return ptr, x, rows, n, row // eb
+
+
+def compute_ntt_batch(device_id, inout, order, direction, ntt_type, field="gl64", stream=None):
+    """sppark_ntt_batch, in place: every row of the 2-D |inout| (numpy array or torch tensor, host or device; rows of 2^k
+    field elements, inner stride 1, any row stride that keeps rows apart -- a torch row view of a wider matrix works)
+    gets what compute_ntt gives it."""
+    p, _k, rows, n, stride = _rows(inout, field, "inout")
+    if n == 0 or n & (n - 1):
+        raise ValueError("the row length is not a power of 2")
+    L = ffi.load(field)
+    ffi.check(L, L.sppark_ntt_batch(device_id, p, n.bit_length() - 1, rows, stride, int(order), int(direction), int(ntt_type), stream))
+    return inout
+
+
+def LDE_batch(device_id, inout, lg_domain_size, lg_blowup, field="gl64", aux_out=None, stream=None):
+    """sppark_lde_batch, in place: |inout| (host or device) is (batch, 2^(lg_domain_size+lg_blowup)) with packed rows, each
+    row's first 2^lg_domain_size elements the evaluations; each row gets what LDE gives it.  aux_out (optional, (batch,
+    2^lg_domain_size), packed) receives the coefficients."""
+    p, _k, rows, n, stride = _rows(inout, field, "inout")
+    if n != 1 << (lg_domain_size + lg_blowup) or stride != n:
+        raise ValueError("inout must be (batch, 2^(lg_domain_size+lg_blowup)) with packed rows")
+    a = None
+    if aux_out is not None:
+        a, _k2, arows, an, astride = _rows(aux_out, field, "aux_out")
+        if arows != rows or an != 1 << lg_domain_size or astride != an:
+            raise ValueError("aux_out must be (batch, 2^lg_domain_size) with packed rows")
+    L = ffi.load(field)
+    ffi.check(L, L.sppark_lde_batch(device_id, p, lg_domain_size, lg_blowup, rows, a, stream))
+    return inout

@@ -145,12 +145,38 @@ KERNEL64(k_mad_four_chains,
     "v_mad_u64_u32 %0, vcc, %8, %9, %0\n v_mad_u64_u32 %1, vcc, %10, %11, %1\n v_mad_u64_u32 %2, vcc, %12, %13, %2\n v_mad_u64_u32 %3, vcc, %14, %15, %3\n"
     "v_mad_u64_u32 %0, vcc, %9, %10, %0\n v_mad_u64_u32 %1, vcc, %11, %12, %1\n v_mad_u64_u32 %2, vcc, %13, %14, %2\n v_mad_u64_u32 %3, vcc, %15, %8, %3\n")
 
+// The mechanism behind montx_dev's column blocks (ff/montx_blocks.hpp), isolated: the SAME 16 multiply-adds on two
+// alternating accumulators per iteration, written as eight chained pair statements (montx_dev::macx2 until round 7:
+// hipcc pads an s_nop 0 after every asm statement whose result the next instruction touches -- it cannot see inside)
+// and as ONE statement (a column block: no pad inside).  Not volatile, as in the product; the accumulators are live out.
+#define PAIR(x0, y0, x1, y1) asm("v_mad_u64_u32 %0, vcc, %2, %3, %0\n\tv_mad_u64_u32 %1, vcc, %4, %5, %1" \
+                                 : "+v"(A0), "+v"(A1) : "v"(x0), "v"(y0), "v"(x1), "v"(y1) : "vcc")
+#define KERNEL_PAIRS(name, BODY)                                                        \
+__global__ __launch_bounds__(256) void name(u32* out, u32 seed, int iters)              \
+{                                                                                       \
+    u64 A0 = seed + threadIdx.x, A1 = A0 * 3;                                           \
+    u32 b0 = (u32)A0 ^ 0x9e3779b9u, b1 = (u32)A1 ^ 0x7f4a7c15u, b2 = b0 + 1, b3 = b1 + 2, b4 = b0 + 3, b5 = b1 + 4, b6 = b0 + 5, b7 = b1 + 6; \
+    _Pragma("unroll 1")                                                                 \
+    for (int i = 0; i < iters; i++) { BODY }                                            \
+    out[blockIdx.x * 256 + threadIdx.x] = (u32)(A0 ^ A1) ^ b0 ^ b1 ^ b2 ^ b3 ^ b4 ^ b5 ^ b6 ^ b7; \
+}
+KERNEL_PAIRS(k_mad_pairs_statements,
+    PAIR(b0, b1, b2, b3); PAIR(b4, b5, b6, b7); PAIR(b1, b2, b3, b4); PAIR(b5, b6, b7, b0);
+    PAIR(b0, b1, b2, b3); PAIR(b4, b5, b6, b7); PAIR(b1, b2, b3, b4); PAIR(b5, b6, b7, b0);)
+KERNEL_PAIRS(k_mad_pairs_block,
+    asm("v_mad_u64_u32 %0, vcc, %2, %3, %0\n\tv_mad_u64_u32 %1, vcc, %4, %5, %1\n\tv_mad_u64_u32 %0, vcc, %6, %7, %0\n\tv_mad_u64_u32 %1, vcc, %8, %9, %1\n\t"
+        "v_mad_u64_u32 %0, vcc, %3, %4, %0\n\tv_mad_u64_u32 %1, vcc, %5, %6, %1\n\tv_mad_u64_u32 %0, vcc, %7, %8, %0\n\tv_mad_u64_u32 %1, vcc, %9, %2, %1\n\t"
+        "v_mad_u64_u32 %0, vcc, %2, %3, %0\n\tv_mad_u64_u32 %1, vcc, %4, %5, %1\n\tv_mad_u64_u32 %0, vcc, %6, %7, %0\n\tv_mad_u64_u32 %1, vcc, %8, %9, %1\n\t"
+        "v_mad_u64_u32 %0, vcc, %3, %4, %0\n\tv_mad_u64_u32 %1, vcc, %5, %6, %1\n\tv_mad_u64_u32 %0, vcc, %7, %8, %0\n\tv_mad_u64_u32 %1, vcc, %9, %2, %1"
+        : "+v"(A0), "+v"(A1) : "v"(b0), "v"(b1), "v"(b2), "v"(b3), "v"(b4), "v"(b5), "v"(b6), "v"(b7) : "vcc");)
+
 typedef void (*kern_t)(u32*, u32, int);
 struct entry { const char* name; kern_t k; };
 static entry table[] = {
     {"v_add_u32", k_add_u32}, {"v_add_u32 + s_nop 0 (VALU only counted)", k_add_nop0}, {"v_add_u32 + s_nop 1 (VALU only counted)", k_add_nop1}, {"v_add_u32 + s_add_u32 (VALU only counted)", k_add_salu}, {"v_add_co + v_addc_co (vcc)", k_addco_vcc_pairs}, {"v_add_co + v_addc_co (sgpr pairs)", k_addco_sgpr_pairs},
     {"v_add_co_u32 (vcc, carry unused)", k_addco_only_vcc}, {"v_lshl_add_u64", k_lshl_add_u64}, {"v_add3_u32", k_add3_u32},
-    {"v_cmp_lt_u32 + v_cndmask_b32", k_cmp_cndmask}, {"v_mad_u64_u32 (8 chains)", k_mad_u64_u32}, {"v_mad_u64_u32, 1 dependent chain", k_mad_one_chain}, {"v_mad_u64_u32, 2 dependent chains", k_mad_two_chains}, {"v_mad_u64_u32, 4 dependent chains", k_mad_four_chains}, {"v_mad_u64_u32 + v_addc_co (vcc)", k_mad_u64_u32_carry}, {"v_mul_lo_u32", k_mul_lo_u32},
+    {"v_cmp_lt_u32 + v_cndmask_b32", k_cmp_cndmask}, {"v_mad_u64_u32 (8 chains)", k_mad_u64_u32}, {"v_mad_u64_u32, 1 dependent chain", k_mad_one_chain}, {"v_mad_u64_u32, 2 dependent chains", k_mad_two_chains}, {"v_mad_u64_u32, 4 dependent chains", k_mad_four_chains},
+    {"2 chains, 8 pair statements (padded)", k_mad_pairs_statements}, {"2 chains, 1 block statement", k_mad_pairs_block}, {"v_mad_u64_u32 + v_addc_co (vcc)", k_mad_u64_u32_carry}, {"v_mul_lo_u32", k_mul_lo_u32},
     {"v_mul_u32_u24", k_mul_u32_u24}, {"v_mad_u32_u24", k_mad_u32_u24}, {"v_mul_hi_u32_u24", k_mul_hi_u32_u24},
     {"alignbit/lshrrev/and mix", k_alignbit_and}, {"v_pk_add_u16", k_pk_add_u16},
 };

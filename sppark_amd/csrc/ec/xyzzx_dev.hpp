@@ -46,19 +46,39 @@ template<class P, int LB> struct affine_loader<montx_dev<P, LB>> {
     // profiles/r02_pmc_traffic.json)
     static constexpr unsigned RAW = 2 * F::NL * 4;
     static constexpr unsigned STRIDE = RAW <= 64 ? 64 : RAW <= 128 ? 128 : ((RAW + 15) / 16) * 16;
-    template<bool FLAGGED>
-    SPPARK_DEVFN static affine_dev<F> load(const unsigned char* base, size_t idx, unsigned)
+    // The record as it lies in memory, no word of it read: what a prefetch keeps in flight.  A gather whose registers
+    // nothing touches costs no wait until decode() -- load() = decode(load_raw()) reads the flag word at once and so
+    // waits for the first of its loads where it stands.
+    struct raw_t {
+        u32 w[(RAW + 15) / 16 * 4];
+        // waits for the loads without reading a word: an empty statement that names every register
+        SPPARK_DEVFN void landed() const
+        {
+#if defined(__HIP_DEVICE_COMPILE__)
+            #pragma unroll
+            for (unsigned i = 0; i < (RAW + 15) / 16 * 4; i++) asm volatile("" :: "v"(w[i]));
+#endif
+        }
+    };
+    SPPARK_DEVFN static raw_t load_raw(const unsigned char* base, size_t idx)
     {
         const uint4* q = reinterpret_cast<const uint4*>(base + idx * (size_t)STRIDE);
-        u32 w[(RAW + 15) / 16 * 4];
+        raw_t r;
         #pragma unroll
-        for (unsigned i = 0; i < (RAW + 15) / 16; i++) { uint4 v = q[i]; w[4*i] = v.x; w[4*i+1] = v.y; w[4*i+2] = v.z; w[4*i+3] = v.w; }
+        for (unsigned i = 0; i < (RAW + 15) / 16; i++) { uint4 v = q[i]; r.w[4*i] = v.x; r.w[4*i+1] = v.y; r.w[4*i+2] = v.z; r.w[4*i+3] = v.w; }
+        return r;
+    }
+    SPPARK_DEVFN static affine_dev<F> decode(const raw_t& r)
+    {
         affine_dev<F> a;
-        a.X = F::from_wire(w); a.Y = F::from_wire(w + F::NL);
+        a.X = F::from_wire(r.w); a.Y = F::from_wire(r.w + F::NL);
         a.inf = (a.X.l[F::NL - 1] >> 31) != 0;
         a.X.l[F::NL - 1] &= 0x7fffffffu;
         return a;
     }
+    template<bool FLAGGED>
+    SPPARK_DEVFN static affine_dev<F> load(const unsigned char* base, size_t idx, unsigned)
+    {   return decode(load_raw(base, idx));   }
     // one work item of the conversion pass: standard wire point -> internal record
     template<bool FLAGGED>
     SPPARK_DEVFN static void convert(unsigned char* dst, const unsigned char* src, size_t idx, unsigned stride)

@@ -123,6 +123,10 @@ void k_breakdown(u32* __restrict__ digits, const u32* __restrict__ scalars,
 // first run, slot 1 = last run); runs strictly inside are complete buckets and
 // are stored straight into buckets[key].
 // ---------------------------------------------------------------------------
+// the prefetched record of the fields that have a raw form (ec/xyzzx_dev.hpp); empty otherwise
+template<class FP, bool ON> struct gather_raw { struct type {}; };
+template<class FP> struct gather_raw<FP, true> { typedef typename affine_loader<FP>::raw_t type; };
+
 template<class FP, bool FLAGGED>
 SPPARK_DEVFN void accumulate_chunk(xyzz_mem<FP::N>* buckets, u32* rec_key, xyzz_mem<FP::N>* rec_pt,
                                    const unsigned char* points, unsigned stride,
@@ -147,7 +151,10 @@ SPPARK_DEVFN void accumulate_chunk(xyzz_mem<FP::N>* buckets, u32* rec_key, xyzz_
         unsigned mid = (lo + hi) >> 1;
         if (o[mid] <= p) lo = mid; else hi = mid;
     }
-    unsigned b = lo, next = o[b + 1];
+    // The bucket offsets run one boundary ahead: next = o[b+1], next2 = o[b+2].  A boundary takes next from the register
+    // and only ISSUES the load of the new next2, which nothing reads before the following boundary.  (o has NB + 1
+    // entries: in the last bucket next = o[NB] = total is never reached and next2 re-reads it.)
+    unsigned b = lo, next = o[b + 1], next2 = o[b + 2 < NB ? b + 2 : NB];
 
     const u32* src = sorted + (size_t)w_local * n;
     xyzz_dev<FP> acc;
@@ -157,37 +164,58 @@ SPPARK_DEVFN void accumulate_chunk(xyzz_mem<FP::N>* buckets, u32* rec_key, xyzz_
     u32 e = src[p];
     affine_dev<FP> pt = load_affine<FP, FLAGGED>(points, e & 0x7fffffffu, stride);
     acc.set(pt, e >> 31);
-    // PREFETCH: the gather of entry p+1 is issued before the addition of entry p, so its latency
-    // hides behind ~20k cycles of arithmetic.  It costs a second point in registers: worth it for
-    // the reduced-radix field (2 waves/SIMD either way, +2 %), not for alt_bn128 (would drop from
-    // 4 to 3 waves/SIMD: 53 -> 71 ms) or Fp2.
-    // (Three waves per SIMD instead of two -- __launch_bounds__(256, 3), 168 registers -- were measured
-    // with the compiler's allocation: 42 spilled registers without this prefetch, 93 with it, 29 with
-    // single-chain products on top; 174 / 200 ms against 112 ms.  The prefetch itself is worth 1 %:
-    // 113.4 vs 112.4 ms.  profiles/r02_msm_accumulate_waves_ab.log)
+    // PREFETCH: the gather of entry p+1 is issued before the addition of entry p and kept RAW (affine_loader::raw_t):
+    // no instruction reads a gathered register until decode() at the top of the next iteration, where the gather is one
+    // whole addition (~20k cycles) old.  It costs a second point in registers: worth it for the reduced-radix field
+    // (2 waves/SIMD either way), not for alt_bn128 (would drop from 4 to 3 waves/SIMD: 53 -> 71 ms) or Fp2.
+    // (Until round 8 the prefetch was decoded where it was issued: the flag bit sits in the first of the seven loads, so
+    // every iteration waited one gather round trip before its addition, and the prefetch measured 1 %: 113.4 vs 112.4 ms,
+    // profiles/r02_msm_accumulate_waves_ab.log.  What the raw form and the offsets kept ahead are worth:
+    // profiles/r08_accumulate_waits_bench_ab.log.)
+    // (Three waves per SIMD instead of two -- __launch_bounds__(256, 3), 168 registers -- were measured with the
+    // compiler's allocation: 42 spilled registers without this prefetch, 93 with it, 29 with single-chain products on
+    // top; 174 / 200 ms against 112 ms.)
     constexpr bool PREFETCH = field_is_montx<FP>::value;
     u32 e_next = 0, e_next2 = 0;                    // the index list runs two entries ahead, so that the
-    affine_dev<FP> pt_next = pt;                    // gather's address never waits for its own load
-    if (PREFETCH && p + 1 < end) { e_next = src[p + 1]; pt_next = load_affine<FP, FLAGGED>(points, e_next & 0x7fffffffu, stride); }
-    if (PREFETCH && p + 2 < end) e_next2 = src[p + 2];
+    typename gather_raw<FP, PREFETCH>::type raw_next = {};      // gather's address never waits for its own load
+    // (past the run's end the prefetches re-read its last entry instead of being skipped: a load that is always issued
+    // lands in the register the loop carries; a skipped one made the compiler copy the whole record round)
+    const unsigned last = end - 1;
+    if constexpr (PREFETCH) {
+        e_next = src[p + 1 < last ? p + 1 : last];
+        raw_next = affine_loader<FP>::load_raw(points, e_next & 0x7fffffffu);
+        e_next2 = src[p + 2 < last ? p + 2 : last];
+    }
+    // The loop's first instruction waits for everything outstanding anyway (e_next2).  Waiting for the first gather here,
+    // before the loop, gives the compiler's wait-count analysis a clean state at the loop's entry: with that gather still in
+    // flight there it left counted waits behind the gather INSIDE the loop, which in an iteration that flushes wait for the
+    // stores.
+    if constexpr (PREFETCH) raw_next.landed();
     for (p++; p < end; p++) {
-        if (PREFETCH) {
-            e = e_next; pt = pt_next;
-            if (p + 1 < end) { e_next = e_next2; pt_next = load_affine<FP, FLAGGED>(points, e_next & 0x7fffffffu, stride); }
-            if (p + 2 < end) e_next2 = src[p + 2];
+        if constexpr (PREFETCH) {
+            e = e_next; pt = affine_loader<FP>::decode(raw_next);
         } else {
             e = src[p];
             pt = load_affine<FP, FLAGGED>(points, e & 0x7fffffffu, stride);
         }
-        if (p == next) {                            // bucket boundary: flush
+        // A bucket boundary flushes BEFORE the gather and the addition of this iteration are issued, and restarts the
+        // sum as infinity + pt (madd from infinity is set(), bit for bit): the stores and the offset load then have the
+        // whole addition to land and nothing below waits for them.
+        if (p == next) {
             const u32 key = w * NB + b;
             if (first_run) { acc.store(&rec_pt[rec0]); slot0_key = key; first_run = false; }
             else           acc.store(&buckets[key]);
-            do { b++; next = o[b + 1]; } while (p == next);
-            acc.set(pt, e >> 31);
-        } else {
-            acc.madd(pt, e >> 31);
+            b++; next = next2;
+            if (p == next) do { b++; next = o[b + 1]; } while (p == next);                  // empty buckets: rare, may wait
+            next2 = o[b + 2 < NB ? b + 2 : NB];
+            acc.set_inf();
         }
+        if constexpr (PREFETCH) {
+            e_next = e_next2;
+            raw_next = affine_loader<FP>::load_raw(points, e_next & 0x7fffffffu);
+            e_next2 = src[p + 2 < last ? p + 2 : last];
+        }
+        acc.madd(pt, e >> 31);
     }
     const u32 key = w * NB + b;
     if (first_run) { acc.store(&rec_pt[rec0]); rec_key[rec0] = key; rec_key[rec0 + 1] = KEY_NONE; }
@@ -476,10 +504,29 @@ SPPARK_DEVFN void bucket_level1_item(xyzz_mem<FP::N>* A, xyzz_mem<FP::N>* Wt, co
     const unsigned w = id / nchunks, u = id % nchunks;
     const xyzz_mem<FP::N>* row = buckets + (size_t)w * NB + (size_t)u * K;
     const u32* o = off ? off + (size_t)w * (NB + 1) + (size_t)u * K : nullptr;
-    xyzz_dev<FP> acc = bucket_load<FP>(row, o, K - 1), ret = acc;
+    // The chunk's K + 1 offsets are read once, all in flight together, and kept as one bit per bucket ("empty"): inside
+    // the chain a bucket then costs ONE dependent load, its own, instead of two offsets, a wait, and then the bucket.
+    // (Chunks of up to LEVEL1_BITS buckets; a longer chunk asks the offsets bucket by bucket as before.  The bucket
+    // itself is not prefetched: the kernel is at its register limit.)
+    constexpr unsigned LEVEL1_BITS = 16;
+    const bool bits = o != nullptr && K <= LEVEL1_BITS;
+    u32 empty = 0;
+    if (bits) {
+        u32 ov[LEVEL1_BITS + 1];
+        #pragma unroll
+        for (unsigned j = 0; j <= LEVEL1_BITS; j++) ov[j] = o[j < K ? j : K];
+        #pragma unroll
+        for (unsigned j = 0; j < LEVEL1_BITS; j++) empty |= (u32)(ov[j + 1] == ov[j]) << j;
+    }
+    auto load = [&](unsigned j) {
+        if (!bits) return bucket_load<FP>(row, o, j);
+        if ((empty >> j) & 1) { xyzz_dev<FP> z; z.set_inf(); return z; }
+        return xyzz_dev<FP>::load(&row[j]);
+    };
+    xyzz_dev<FP> acc = load(K - 1), ret = acc;
     for (unsigned j = K - 1; j--;) {
-        if (LAT) { bucket_add_fast<FP>(acc, bucket_load<FP>(row, o, j)); bucket_add_fast<FP>(ret, acc); }
-        else     { bucket_add<FP>(acc, bucket_load<FP>(row, o, j)); bucket_add<FP>(ret, acc); }
+        if (LAT) { bucket_add_fast<FP>(acc, load(j)); bucket_add_fast<FP>(ret, acc); }
+        else     { bucket_add<FP>(acc, load(j)); bucket_add<FP>(ret, acc); }
     }
     acc.store(&A[id]); ret.store(&Wt[id]);
 }

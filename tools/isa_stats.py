@@ -7,6 +7,13 @@ whose demangled name contains the substring) the register / LDS / scratch figure
 descriptor's metadata and a STATIC count of its instructions by opcode (straight-line count of the
 emitted code, loops counted once).  --classes groups the opcodes the way DESIGN.md's instruction
 accounts do; --dump writes the disassembly of the selected kernels to stdout.
+
+    python tools/isa_stats.py <unit>.s [kernel-name-substring] --waits
+
+reads the ASSEMBLY hipcc writes with --cuda-device-only -S (it keeps the block labels and the loop each block belongs to,
+which a disassembly does not) and lists, for the main loop of every selected kernel, its vector-memory instructions and
+its `s_waitcnt vmcnt` in program order: where a wave can be parked on memory.  asm_kernels() / main_loop() / loop_waits()
+are what tests/test_accumulate_waits.py asserts on.
 """
 import collections
 import os
@@ -92,10 +99,110 @@ def metadata(co):
     return out
 
 
+def asm_kernels(path):
+    """{symbol: {"ins": [...], "NumVgprs": n, "ScratchSize": n, "Occupancy": n}} of an assembly file (hipcc -S).  One entry of
+    "ins" per instruction: {"op", "args", "block": label of its basic block, "loop": header label of the OUTERMOST loop the
+    block is in (None outside loops), "depth": loop depth of the block}."""
+    out, cur, sym = collections.OrderedDict(), None, None
+    block, loop, depth = None, None, 0
+    for line in open(path):
+        line = line.rstrip("\n")
+        m = re.match(r"^([A-Za-z_][\w$.]*):\s*(?:;.*)?$", line)
+        if m and not m.group(1).startswith((".L", "__hip")):                # a function's entry label
+            sym = m.group(1)
+            cur = out[sym] = {"ins": []}
+            block, loop, depth = sym, None, 0
+            continue
+        if cur is None:
+            continue
+        m = re.match(r"^; (NumVgprs|ScratchSize|Occupancy): (\d+)", line)
+        if m:
+            out[sym][m.group(1)] = int(m.group(2))
+            continue
+        m = re.match(r"^(\.LBB\d+_\d+):\s*(?:;\s*(.*))?$", line) or re.match(r"^; %bb\.(\d+):\s*(?:;\s*(.*))?$", line)
+        if m:
+            block, note = m.group(1), m.group(2) or ""
+            # "=>This Loop Header: Depth=1" | "in Loop: Header=BB0_25 Depth=1" | "Parent Loop BB0_25 Depth=1" (+ a line
+            # "=>  This Inner Loop Header: Depth=2" below it) | nothing: not in a loop
+            h = re.search(r"in Loop: Header=(BB\d+_\d+) Depth=(\d+)", note)
+            if "This Loop Header" in note:
+                loop, depth = block.replace(".L", ""), 1
+            elif h:
+                depth = int(h.group(2))
+                loop = h.group(1) if depth == 1 else loop
+            elif "Parent Loop" in note:
+                loop, depth = re.search(r"Parent Loop (BB\d+_\d+)", note).group(1), 2
+            else:
+                loop, depth = None, 0
+            continue
+        m = re.match(r"^\s+;\s+=>\s*This Inner Loop Header: Depth=(\d+)", line)
+        if m:
+            depth = int(m.group(1))
+            continue
+        m = re.match(r"^\t([a-z]\w*)\b\s*(.*?)\s*(?:;.*)?$", line)
+        if m and sym in out and "Occupancy" not in out[sym]:
+            cur["ins"].append({"op": m.group(1), "args": m.group(2), "block": block, "loop": loop, "depth": depth})
+    return out
+
+
+def main_loop(kernel):
+    """the instructions of the kernel's largest outermost loop, in program order (inner loops included: depth 2 and more)"""
+    size = collections.Counter(i["loop"] for i in kernel["ins"] if i["loop"])
+    if not size:
+        return []
+    top = size.most_common(1)[0][0]
+    return [i for i in kernel["ins"] if i["loop"] == top]
+
+
+def is_vmem(op):
+    return op.startswith(("global_", "buffer_", "flat_", "scratch_"))
+
+
+def loop_waits(loop):
+    """[(position in the loop, kind, text, depth)] of the loop's vector-memory instructions ("load" / "store"), its
+    `s_waitcnt vmcnt` ("wait") and the first v_mad_u64_u32 after each of them ("mad": where arithmetic resumes)"""
+    ev, want_mad = [], False
+    for k, i in enumerate(loop):
+        op, args = i["op"], i["args"]
+        if op == "s_waitcnt" and "vmcnt" in args:
+            ev.append((k, "wait", "s_waitcnt " + args, i["depth"])); want_mad = True
+        elif is_vmem(op):
+            ev.append((k, "store" if "store" in op else "load", op + " " + args, i["depth"])); want_mad = True
+        elif op == "v_mad_u64_u32" and want_mad:
+            ev.append((k, "mad", "v_mad_u64_u32 (arithmetic resumes)", i["depth"])); want_mad = False
+    return ev
+
+
+def print_waits(path, want):
+    for sym, kern in asm_kernels(path).items():
+        dem = subprocess.run(["c++filt", sym], capture_output=True, text=True).stdout.strip()
+        if (want and want not in dem and want not in sym) or "NumVgprs" not in kern:
+            continue
+        loop = main_loop(kern)
+        ops = collections.Counter(i["op"] for i in kern["ins"])
+        print("== %s" % dem[:160])
+        print("   vgpr %s  scratch %s B  waves/SIMD %s  v_mad_u64_u32 %d  |  main loop: %d instructions, %d v_mov_b64, %d s_waitcnt vmcnt"
+              % (kern.get("NumVgprs"), kern.get("ScratchSize"), kern.get("Occupancy"), ops["v_mad_u64_u32"], len(loop),
+                 sum(i["op"].startswith("v_mov_b64") for i in loop), sum(i["op"] == "s_waitcnt" and "vmcnt" in i["args"] for i in loop)))
+        run = None
+        for k, kind, text, depth in loop_waits(loop) + [(None, None, None, None)]:
+            # runs of alike loads / stores on one line
+            head = text.split(" ")[0] if kind in ("load", "store") else None
+            if run and (head != run[1] or depth != run[3]):
+                print("   %6d  %s%s%s" % (run[0], "    " * (run[3] - 1), run[1], "  x %d" % run[2] if run[2] > 1 else ""))
+                run = None
+            if kind in ("load", "store"):
+                run = [k, head, 1, depth] if run is None else [run[0], run[1], run[2] + 1, depth]
+            elif kind:
+                print("   %6d  %s%s" % (k, "    " * (depth - 1), text))
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     path = args[0]
     want = args[1] if len(args) > 1 else ""
+    if "--waits" in sys.argv:
+        return print_waits(path, want)
     co = code_object(path)
     meta = metadata(co)
     dis = subprocess.run([LLVM + "/llvm-objdump", "-d", "--no-show-raw-insn", co], capture_output=True, text=True).stdout

@@ -35,6 +35,7 @@ MSM_TUS = ["api/msm_api.hip", "msm/k_accumulate.hip", "msm/k_reduce.hip",
 MSM_G1_TUS = [t for t in MSM_TUS if "SPPARK_G2" not in t]      # curves without a G2 (Pasta)
 NTT_TUS = ["api/ntt_api.hip", "ntt/k_ntt_pass.hip:SPPARK_NTT_DIF=1", "ntt/k_ntt_pass.hip:SPPARK_NTT_DIF=0",
            "ntt/k_ntt_r64.hip:SPPARK_NTT_DIF=1", "ntt/k_ntt_r64.hip:SPPARK_NTT_DIF=0"]       # single-word fields: radix-64 plan
+DEVTEST_TUS = ["api/devtest_api.hip", "api/devtest_g2_api.hip"]
 
 TARGETS = {
     "bls12_381": ("FEATURE_BLS12_381", MSM_TUS),
@@ -51,11 +52,13 @@ TARGETS = {
     "gl64_plonky2":   ("FEATURE_GOLDILOCKS -DGOLDILOCKS_PLONKY2", NTT_TUS),
     "bb31_canonical": ("FEATURE_BABY_BEAR -DBABY_BEAR_CANONICAL", NTT_TUS),
     # test-only libraries (device test hooks + micro-benchmarks): never linked into the product ones
-    "bls12_381_devtest": ("FEATURE_BLS12_381", ["api/devtest_api.hip"]),
-    "bn254_devtest":     ("FEATURE_BN254", ["api/devtest_api.hip"]),
-    "bls12_377_devtest": ("FEATURE_BLS12_377", ["api/devtest_api.hip"]),
-    "pallas_devtest":    ("FEATURE_PALLAS", ["api/devtest_api.hip"]),
-    "vesta_devtest":     ("FEATURE_VESTA", ["api/devtest_api.hip"]),
+    # (api/devtest_g2_api.hip: the G2 hooks and the product forms of the bucket field; on the curves without a G2 -- SPPARK_NO_G2 --
+    # only the latter is compiled)
+    "bls12_381_devtest": ("FEATURE_BLS12_381", DEVTEST_TUS),
+    "bn254_devtest":     ("FEATURE_BN254", DEVTEST_TUS),
+    "bls12_377_devtest": ("FEATURE_BLS12_377", DEVTEST_TUS),
+    "pallas_devtest":    ("FEATURE_PALLAS", DEVTEST_TUS),
+    "vesta_devtest":     ("FEATURE_VESTA", DEVTEST_TUS),
     "gl64_devtest":      ("FEATURE_GOLDILOCKS", ["api/devtest_small_api.hip"]),
     "bb31_devtest":      ("FEATURE_BABY_BEAR", ["api/devtest_small_api.hip"]),
 }
@@ -136,7 +139,7 @@ def build(only=None, force=False, verbose=True, jobs=None):
     # with 8 cores the makespan is then bounded by total work, not by a late long job
     cost = {"msm/k_bucketN.hip": 85, "msm/k_bucket_lat.hip": 95, "msm/k_bucketN.hip:SPPARK_G2": 75, "msm/k_accumulate.hip:SPPARK_G2": 70,
             "ntt/k_ntt_pass.hip:SPPARK_NTT_DIF=0": 68, "ntt/k_ntt_pass.hip:SPPARK_NTT_DIF=1": 57,
-            "msm/k_reduce.hip:SPPARK_G2": 54, "msm/k_bucket1.hip:SPPARK_G2": 53, "api/devtest_api.hip": 100,
+            "msm/k_reduce.hip:SPPARK_G2": 54, "msm/k_bucket1.hip:SPPARK_G2": 53, "api/devtest_api.hip": 100, "api/devtest_g2_api.hip": 130,
             "msm/k_bucket1.hip": 35, "api/msm_api.hip": 28, "msm/k_accumulate.hip": 25, "msm/k_reduce.hip": 24}
     todo.sort(key=lambda job: -cost.get(job[0], 5) * (2 if "BLS12" in job[2] else 1))
     if todo:

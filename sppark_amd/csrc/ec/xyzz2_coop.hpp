@@ -57,7 +57,7 @@ template<class F2> struct g2c_ctx {
 };
 
 // component |role| of a * b from this wave's components (a, b) and the other wave's (ao, bo); contract of
-// fp2x_dev::mul<KA>: operands normalised, a < (KA - 1) p
+// fp2x_dev::mul<KA>: operands normalised, a <= (KA - 1) p
 template<class F2, int KA, unsigned ROLE>
 SPPARK_DEVFN typename F2::fp g2c_mul(const typename F2::fp& a, const typename F2::fp& ao,
                                      const typename F2::fp& b, const typename F2::fp& bo)
@@ -165,18 +165,18 @@ template<class F2> struct g2c_bucket {
         const bool from_point = restart || (ZZ.limbs_all_zero() && c.other_flag() != 0);
         const fp U2 = g2c_mul<F2, 3, ROLE>(p.X, c.other(0), ZZ, c.other(2));           // < 2 p, n
         fp S2 = g2c_mul<F2, 3, ROLE>(p.Y, c.other(1), ZZZ, c.other(3));
-        if (negate) S2 = fp::template neg<3>(S2).norm();                            // < 3 p
+        if (negate) S2 = fp::template neg<3>(S2).norm();                            // <= 3 p (3 p itself where S2 is 0)
         const fp Pd = fp::template sub<KX>(U2, X).norm();                           // < 12 p
-        const fp Rd = fp::template sub<KY>(S2, Y).norm();                           // < 9 p
+        const fp Rd = fp::template sub<KY>(S2, Y).norm();                           // <= 9 p
         // -- exchange 2: P, R and whether they vanish
         c.open();
         c.put(0, Pd); c.put(1, Rd);
-        c.put_flag((Pd.template is_zero_mod<12>() ? 1u : 0u) | (Rd.template is_zero_mod<9>() ? 2u : 0u));
+        c.put_flag((Pd.template is_zero_mod<12>() ? 1u : 0u) | (Rd.template is_zero_mod<10>() ? 2u : 0u));     // (9 p occurs: -0 - 0)
         c.shut();
         const u32 zf = c.ex->flag[0][c.lane] & c.ex->flag[1][c.lane];               // both components vanish
         const bool p_zero = (zf & 1u) != 0, r_zero = (zf & 2u) != 0;
         const fp PP = g2c_sqr<F2, 13, ROLE>(Pd, c.other(0));                           // < 2 p
-        const fp RR = g2c_sqr<F2, 10, ROLE>(Rd, c.other(1));
+        const fp RR = g2c_sqr<F2, 10, ROLE>(Rd, c.other(1));                           // (Rd = 9 p itself is admissible)
         // -- exchange 3: PP and X (slot 0 still holds P, slot 2 ZZ: re-read, not kept in registers)
         c.open(); c.put(1, PP); c.put(3, X); c.shut();
         const fp PPo = c.other(1);

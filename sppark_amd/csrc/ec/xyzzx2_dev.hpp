@@ -74,13 +74,13 @@ template<class P, int LB> struct xyzz_dev<fp2x_dev<P, LB>> {
 
         F U2 = F::template mul<3>(p.X, ZZ);                         // < 2 p, n
         F S2 = F::template mul<3>(p.Y, ZZZ);
-        if (negate) S2 = F::template neg<3>(S2).norm();             // < 3 p
+        if (negate) S2 = F::template neg<3>(S2).norm();             // <= 3 p (3 p itself where a component of S2 is 0)
         const F Pd = F::template sub<KX>(U2, X).norm();             // U2 - X      < 12 p
-        const F Rd = F::template sub<KY>(S2, Y).norm();             // +-S2 - Y    < 9 p
+        const F Rd = F::template sub<KY>(S2, Y).norm();             // +-S2 - Y    <= 9 p
 
         if (!Pd.template is_zero_mod<12>()) {                       // fast path
             const F PP  = Pd.template sqr<13>();                    // < 2 p
-            const F RR  = Rd.template sqr<10>();
+            const F RR  = Rd.template sqr<10>();                    // (Rd = 9 p itself is admissible: fp2x_dev::sqr)
             const F PPP = F::template mul<13>(Pd, PP);
             const F Q   = F::template mul<KX>(X, PP);
             const F T   = PPP + Q + Q;                              // < 6 p, limbs < 3 * 2^LB
@@ -90,7 +90,7 @@ template<class P, int LB> struct xyzz_dev<fp2x_dev<P, LB>> {
             ZZ  = F::template mul<3>(ZZ, PP);
             ZZZ = F::template mul<3>(ZZZ, PPP);
             X = X3;
-        } else if (Rd.template is_zero_mod<9>()) {                  // same point: 2 * p
+        } else if (Rd.template is_zero_mod<10>()) {                 // same point: 2 * p  (9 p occurs: -0 - 0 in one component)
             dbl_affine(p.X, negate ? F::template neg<3>(p.Y).norm() : p.Y);
         } else {
             set_inf();

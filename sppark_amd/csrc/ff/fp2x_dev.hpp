@@ -55,7 +55,10 @@ template<class P, int LB> struct fp2x_dev {
         else { static_assert(P::FP2_NR == 5, "non-residue"); return (x + x + x + x + x).norm(); }
     }
 
-    // a * b.  a, b normalised; a < (KA - 1) p.  Result normalised, < 2 p:
+    // a * b.  a, b normalised; a <= (KA - 1) p.  (The bound itself is admissible, and it occurs: K p - 0 = K p is what
+    // neg<K> makes of a zero component.  montx_dev::neg / sub state "< (K - 1) p" so that no limb underflows; at (K - 1) p
+    // the difference is p, and limb by limb the fat K p still dominates: its top limb exceeds that of (K - 1) p by the
+    // top limb of p, which is >= 3 on the three fields, less the one it lends.)  Result normalised, < 2 p:
     // (a0 b1 + a1 b0) / R + p with a, b < 16 p is < (512 p / R + 1) p.
     template<int KA> SPPARK_DEVFN static fp2x_dev mul(const fp2x_dev& a, const fp2x_dev& b)
     {
@@ -65,7 +68,7 @@ template<class P, int LB> struct fp2x_dev {
         r.c0 = fp::mul_add(a.c0, b.c0, na1, mul_nr(b.c1));
         return r;
     }
-    // a^2.  a normalised, a < (KA - 1) p.  Result normalised, < 2 p.
+    // a^2.  a normalised, a <= (KA - 1) p (as for mul).  Result normalised, < 2 p.
     template<int KA> SPPARK_DEVFN fp2x_dev sqr() const
     {
         if constexpr (P::FP2_NR == 1) {

@@ -209,6 +209,21 @@ def load_devtest(name):
         L.sppark_devtest_bucket_xyzz_op.restype = _Error
         L.sppark_devtest_xyzz_op.argtypes = [ci, vp, vp, vp, sz]
         L.sppark_devtest_xyzz_op.restype = _Error
+        # api/devtest_g2_api.hip: every product form of the bucket field on raw limbs; on the curves with a G2, Fp2 and the
+        # G2 point classes operation by operation
+        L.sppark_devtest_blocks_info.argtypes = [ci, vp]
+        L.sppark_devtest_blocks_info.restype = ci
+        L.sppark_devtest_blocks_run.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp, sz]
+        L.sppark_devtest_blocks_run.restype = _Error
+        if name not in NO_G2:
+            L.sppark_devtest_fp2x_op.argtypes = [ci, ci, vp, vp, vp, sz]
+            L.sppark_devtest_fp2x_op.restype = _Error
+            L.sppark_devtest_fp2_wire_op.argtypes = [ci, vp, vp, vp, sz]
+            L.sppark_devtest_fp2_wire_op.restype = _Error
+            L.sppark_devtest_g2_xyzz_op.argtypes = [ci, ci, vp, vp, vp, sz]
+            L.sppark_devtest_g2_xyzz_op.restype = _Error
+            L.sppark_devtest_g2_chain.argtypes = [ci, vp, vp, vp, sz, sz, vp, sz, ctypes.c_uint]
+            L.sppark_devtest_g2_chain.restype = _Error
     else:
         L.sppark_devtest_small_field_op.argtypes = [ci, vp, vp, vp, sz]
         L.sppark_devtest_small_field_op.restype = _Error

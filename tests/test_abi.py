@@ -42,7 +42,9 @@ def test_header_symbols_exported(libs):
         for s in want:
             assert hasattr(L, s), (name, s)
         # the device test hooks live in separate test libraries (libsppark_*_devtest.so)
-        for s in ("sppark_devtest_field_op", "sppark_devtest_small_field_op", "sppark_devtest_xyzz_op"):
+        for s in ("sppark_devtest_field_op", "sppark_devtest_small_field_op", "sppark_devtest_xyzz_op",
+                  "sppark_devtest_blocks_info", "sppark_devtest_blocks_run", "sppark_devtest_fp2x_op", "sppark_devtest_fp2_wire_op",
+                  "sppark_devtest_g2_xyzz_op", "sppark_devtest_g2_chain"):
             assert not hasattr(L, s), (name, s)
 
 

@@ -51,7 +51,10 @@ def test_register_budget(obj, needle, max_regs):
 @pytest.mark.parametrize("obj", ["bls12_381__msm_k_reduce.hip.o", "bls12_381__msm_k_reduce.hip__SPPARK_G2.o",
                                  "bls12_381__msm_k_bucketN.hip.o", "bls12_381__msm_k_bucketN.hip__SPPARK_G2.o",
                                  "bls12_381__msm_k_bucket1.hip.o", "bls12_381__msm_k_accumulate.hip.o",
-                                 "bls12_381__msm_k_bucket_lat.hip.o", "bn254__msm_k_bucket_lat.hip.o"])      # incl. the cooperative kernels
+                                 "bls12_381__msm_k_bucket_lat.hip.o", "bn254__msm_k_bucket_lat.hip.o",      # incl. the cooperative kernels
+                                 # the device test hooks over Fp2 (they call the outlined Fp2 doubling, too)
+                                 "bls12_381__api_devtest_g2_api.hip.o", "bn254__api_devtest_g2_api.hip.o",
+                                 "bls12_377__api_devtest_g2_api.hip.o"])
 def test_point_arithmetic_kernels_are_one_wave_per_simd_groups(obj):
     """The kernels that do point arithmetic are built for work-groups of <= 256 lanes (one wave per SIMD, up to 512
     registers).  A larger `__launch_bounds__` caps the kernel's registers (1024 lanes: 128) -- the 14-limb addition then

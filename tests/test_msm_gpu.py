@@ -160,6 +160,23 @@ def test_bucket_field_ops(libs):
         assert sum(int(raw[i, k]) << (32 * k) for k in range(12)) == AF[i] * inv256 % Pm
 
 
+def _bucket_operands(O, ffi, L, curve, n):
+    """n wire-form XYZZ accumulators and XYZZ operands on true points of |curve|, with ZZ, ZZZ != 1 (mixed additions by the
+    wire class first), row 3 an accumulator that started at infinity, row 0 equal operands (the doubling inside add)."""
+    fb = O.FP_BYTES[curve]
+    one = np.frombuffer(((1 << (8 * fb)) % O.FP_MODULUS[curve]).to_bytes(fb, "little"), dtype=np.uint8)     # 1 on the wire
+    xa = np.zeros((n, 4 * fb), dtype=np.uint8); xa[:, :2 * fb] = O.g1_gen_points(curve, n, 11); xa[:, 2 * fb:3 * fb] = one; xa[:, 3 * fb:] = one
+    xa[3] = 0
+    # (the operand arrays are held in names: the address of a temporary would be that of freed memory by the time of the call)
+    p13 = O.g1_gen_points(curve, n, 13); p14 = O.g1_gen_points(curve, n, 14)
+    tmp = np.zeros_like(xa)
+    ffi.check(L, L.sppark_devtest_xyzz_op(1, P(tmp), P(xa), P(p13), n)); xa = tmp.copy()
+    xb = np.zeros_like(xa)
+    ffi.check(L, L.sppark_devtest_xyzz_op(1, P(xb), P(xa), P(p14), n))
+    xb[0] = xa[0]
+    return xa, xb
+
+
 def test_bucket_point_ops_bit_exact_with_wire_class(oracle, libs):
     """The loosely-reduced XYZZ formulas (ec/xyzzx_dev.hpp), fed and read back in the wire form,
     give the SAME coordinates bit for bit as the canonical 32-bit-limb class (same formulas,
@@ -174,15 +191,8 @@ def test_bucket_point_ops_bit_exact_with_wire_class(oracle, libs):
     y = int.from_bytes(A[1, fb:].tobytes(), "little")
     B[1] = A[1]; B[1, fb:] = np.frombuffer(((pmod - y) % pmod).to_bytes(fb, "little"), dtype=np.uint8)
     B[2] = 0
-    one = O.field_op(O.FIELD_BLS_FP, 4, O.int_to_limbs(1, fb)).view(np.uint8)
-    xa = np.zeros((n, 4 * fb), dtype=np.uint8); xa[:, :2 * fb] = A; xa[:, 2 * fb:3 * fb] = one; xa[:, 3 * fb:] = one
-    xa[3] = 0
-    # make the accumulators non-trivial (ZZ, ZZZ != 1): a few additions with the wire class first
-    tmp = np.zeros_like(xa)
-    ffi.check(L, L.sppark_devtest_xyzz_op(1, P(tmp), P(xa), P(O.g1_gen_points(curve, n, 13)), n)); xa = tmp.copy()
-    xb = np.zeros_like(xa)
-    ffi.check(L, L.sppark_devtest_xyzz_op(1, P(xb), P(xa), P(O.g1_gen_points(curve, n, 14)), n))
-    xb[0] = xa[0]                                            # equal XYZZ operands -> doubling inside add
+    # accumulators on the points A, made non-trivial (ZZ, ZZZ != 1) by a few additions with the wire class first
+    xa, xb = _bucket_operands(O, ffi, L, curve, n)
     for op, operand in ((0, xb), (1, B), (2, B), (3, None)):
         ref = np.zeros_like(xa); got = np.zeros_like(xa)
         ptr = P(operand) if operand is not None else 0
@@ -190,15 +200,23 @@ def test_bucket_point_ops_bit_exact_with_wire_class(oracle, libs):
         ffi.check(L, L.sppark_devtest_bucket_xyzz_op(op, P(got), P(xa), ptr, n))
         assert (got == ref).all(), op
     # the cooperative forms (ec/xyzz_coop.hpp: four waves per 64 operations), two operations in a row:
-    # (a + b) + b against two serial additions, 2(2a) against two serial doublings; n is not a multiple of 64
-    xb[5] = 0                                                # an operand at infinity on the right as well
-    r1 = np.zeros_like(xa); r2 = np.zeros_like(xa); got = np.zeros_like(xa)
-    ffi.check(L, L.sppark_devtest_xyzz_op(0, P(r1), P(xa), P(xb), n)); ffi.check(L, L.sppark_devtest_xyzz_op(0, P(r2), P(r1), P(xb), n))
-    ffi.check(L, L.sppark_devtest_bucket_xyzz_op(4, P(got), P(xa), P(xb), n))
-    assert (got == r2).all()
-    ffi.check(L, L.sppark_devtest_xyzz_op(3, P(r1), P(xa), 0, n)); ffi.check(L, L.sppark_devtest_xyzz_op(3, P(r2), P(r1), 0, n))
-    ffi.check(L, L.sppark_devtest_bucket_xyzz_op(5, P(got), P(xa), 0, n))
-    assert (got == r2).all()
+    # (a + b) + b against two serial additions, 2(2a) against two serial doublings; n is not a multiple of 64.
+    # On ALL FIVE curves: the hooks are built for each of them and the tail kernels use the cooperative forms on each.
+    for cv, cname in CURVES:
+        Lc = ffi.load_devtest(cname)
+        # The cooperative forms exist where the bucket field is montx_dev (field_is_montx): on every curve.  The hook below
+        # reports field_is_internal, which for a G1 bucket field is the same thing; and were it not, ops 4 and 5 answer
+        # hipErrorNotSupported and ffi.check fails the test -- nothing is skipped.
+        assert Lc.sppark_devtest_bucket_field_limbs() == {48: 14, 32: 9}[O.FP_BYTES[cv]], cname
+        ca, cb = (xa, xb) if cv == curve else _bucket_operands(O, ffi, Lc, cv, n)
+        cb[5] = 0                                            # an operand at infinity on the right as well
+        r1 = np.zeros_like(ca); r2 = np.zeros_like(ca); got = np.zeros_like(ca)
+        ffi.check(Lc, Lc.sppark_devtest_xyzz_op(0, P(r1), P(ca), P(cb), n)); ffi.check(Lc, Lc.sppark_devtest_xyzz_op(0, P(r2), P(r1), P(cb), n))
+        ffi.check(Lc, Lc.sppark_devtest_bucket_xyzz_op(4, P(got), P(ca), P(cb), n))
+        assert (got == r2).all(), cname
+        ffi.check(Lc, Lc.sppark_devtest_xyzz_op(3, P(r1), P(ca), 0, n)); ffi.check(Lc, Lc.sppark_devtest_xyzz_op(3, P(r2), P(r1), 0, n))
+        ffi.check(Lc, Lc.sppark_devtest_bucket_xyzz_op(5, P(got), P(ca), 0, n))
+        assert (got == r2).all(), cname
 
 
 @pytest.mark.parametrize("curve,name", CURVES)

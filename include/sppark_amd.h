@@ -206,15 +206,11 @@ SppError sppark_msm_tune_split(sppark_msm_ctx *ctx, unsigned big_partition);
 /* bucket sums: windows with at most top_items partial sums are finished by the subset-sum kernels
  * (k_bucket_top_bits / k_bucket_top_sum); 0 = automatic (4096), 1 = never */
 SppError sppark_msm_tune_sums(sppark_msm_ctx *ctx, unsigned top_items);
-/* The tail of an MSM.  join: 0 = the record segments of at most eight records (with uniform scalars: all
- * of them) are summed by one launch (k_join_runs) and the fan-in tree only sees the longer ones; 1 = every
- * segment goes through the tree; 2 / 3 = A/B switches: 2 = without the one-launch narrow end of the tree
- * (k_reduce_tail), 3 = without the low-latency bucket-sum kernels for small grids, 4 = without the cooperative (four waves
- * per operation) kernels, 5 = without the piece tree of the small sizes, 6 = the point conversion with one lane per point
- * instead of the coalesced form, 7 = the subset-sum top with a work-group per sum instead of per piece of a sum, 8 = every level of the piece
- * tree a launch of its own (no k_piece_tail_coop), 16 + x = that launch from the first level of at most 2^x work items, 10 = the latency-bound chunked bucket-sum levels with one lane per work
- * item (k_bucket_level1_lat / _levelN_lat) instead of their sums on two / three waves (k_bucket_level1_pipe / _levelN_pipe).  k1: buckets per work item of the first bucket-sum level (a power of
- * two; 0 = the same as the other levels). */
+/* The tail of an MSM.  join: 0 = what ships; any other value is the numeric code of ONE A/B switch that keeps an older
+ * form of a step reachable (1 = every record segment through the fan-in tree instead of k_join_runs, ... 16 + x): the
+ * table of codes is at decode_tail_code() in sppark_amd/csrc/msm/msm_plan.hpp.  Codes the table does not name change
+ * nothing; codes from 80 on are refused (invalid value).  k1: buckets per work item of the first bucket-sum level (a power
+ * of two; 0 = the same as the other levels). */
 SppError sppark_msm_tune_tail(sppark_msm_ctx *ctx, unsigned join, unsigned k1);
 /* Pipeline shape.  groups: the windows are sorted and accumulated in this many groups, the digits +
  * sort of group g+1 on a second stream beside the bucket accumulation of group g (0 / 1 = one group,

@@ -267,9 +267,11 @@ SPPARK_FFI RustError mult_pippenger_fp2_inf(void* out, const void* points, size_
         {
             struct g2k { const char* name; unsigned msm_tunables::*f; };
             static const g2k ks[] = {{"SPPARK_G2_WBITS", &msm_tunables::wbits}, {"SPPARK_G2_L", &msm_tunables::L}, {"SPPARK_G2_F", &msm_tunables::F},
-                                     {"SPPARK_G2_K", &msm_tunables::K}, {"SPPARK_G2_K1", &msm_tunables::K1}, {"SPPARK_G2_TOP", &msm_tunables::top},
-                                     {"SPPARK_G2_JOIN", &msm_tunables::join}};
+                                     {"SPPARK_G2_K", &msm_tunables::K}, {"SPPARK_G2_K1", &msm_tunables::K1}, {"SPPARK_G2_TOP", &msm_tunables::top}
+                                    };
             for (const g2k& k : ks) { const char* e = getenv(k.name); msm->tune.*(k.f) = e ? (unsigned)atoi(e) : 0u; }    // (pooled context: absent = automatic again)
+            const char* e = getenv("SPPARK_G2_JOIN");       // the numeric code of sppark_msm_tune_tail
+            if (!decode_tail_code(e ? (unsigned)atoi(e) : 0u, msm->tune.sw)) HIP_OK(hipErrorInvalidValue);
         }
 #endif
         if (is_device_pointer(points) || is_device_pointer(scalars)) HIP_OK(hipDeviceSynchronize());
@@ -446,13 +448,14 @@ SPPARK_FFI RustError sppark_msm_tune_split(sppark_msm_ctx* ctx, unsigned big_par
 // bucket sums: windows with at most this many partial sums go to the subset-sum top (0 = automatic, 1 = never)
 SPPARK_FFI RustError sppark_msm_tune_sums(sppark_msm_ctx* ctx, unsigned top_items)
 {   return guarded([&] { ctx->impl.tune.top = top_items; });   }
-// the tail of an MSM: join = 1 switches k_join_runs off (every record segment through the fan-in tree);
+// the tail of an MSM: join = the numeric code of an A/B switch (the table at msm_plan.hpp decode_tail_code; 0 = none);
 // k1 = buckets per work item of the first bucket-sum level (a power of two; 0 = as the other levels)
 SPPARK_FFI RustError sppark_msm_tune_tail(sppark_msm_ctx* ctx, unsigned join, unsigned k1)
 {
     return guarded([&] {
-        if (k1 & (k1 - 1)) HIP_OK(hipErrorInvalidValue);
-        ctx->impl.tune.join = join; ctx->impl.tune.K1 = k1;
+        msm_switches sw;
+        if ((k1 & (k1 - 1)) || !decode_tail_code(join, sw)) HIP_OK(hipErrorInvalidValue);
+        ctx->impl.tune.sw = sw; ctx->impl.tune.K1 = k1;
     });
 }
 // pipeline shape: window groups (0 = automatic, 1 = single stream), points per chunk of the
@@ -500,7 +503,7 @@ SPPARK_FFI void sppark_msm_plan_sort(const sppark_msm_ctx* ctx, size_t npoints, 
 {
     msm_plan p = ctx->impl.plan_for(npoints);
     out[0] = p.nslabs; out[1] = p.slab_sz; out[2] = p.IB; out[3] = p.SH; out[4] = p.NG; out[5] = p.G; out[6] = p.K1;
-    out[7] = ctx->impl.piece_tree_cmax(p, p.G > 1, 0);
+    out[7] = ctx->impl.piece_tree_cmax(p);
 }
 SPPARK_FFI RustError sppark_msm_tune_records(sppark_msm_ctx* ctx, unsigned records)
 {   return guarded([&] { if (records > 2) throw hip_error(-(int)hipErrorInvalidValue, "tune_records"); ctx->impl.tune.records = records; });   }

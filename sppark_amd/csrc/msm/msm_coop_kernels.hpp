@@ -16,7 +16,7 @@
 
 namespace sppark_amd {
 
-static constexpr unsigned COOP_NT = 256;        // four waves
+// (COOP_NT = 256 lanes, four waves: msm_thresholds.hpp)
 
 // CAP points in LDS, word-major (lane-contiguous words: conflict-free 4-byte accesses)
 template<class FP, unsigned CAP> struct coop_img {
@@ -61,9 +61,6 @@ SPPARK_DEVFN void coop_tree_sum(coop_img<FP, CAP>* img, unsigned s0, coop_ctx<FP
         coop_barrier();
     }
 }
-
-// (the exchange area of the cooperative operations + an image of COOP_NT / 2 points: 56 KB on fourteen limbs, two work-groups per CU)
-static inline size_t top_bits_coop_lds(size_t nl) { return 2 * 4 * nl * 64 * 4 + 4 * nl * (COOP_NT / 2) * 4; }
 
 // k_bucket_top_bits with the tree and the doubling chain in cooperative form (same per-lane gather, same sums), one work-group
 // per PIECE of a sum (msm_kernels.hpp bucket_top_piece; sb = sp = 1: per sum, as k_bucket_top_bits): part q of window w.
@@ -151,7 +148,6 @@ namespace sppark_amd {
 // The addition at step r is skipped by the whole work-group when no work item has one (__syncthreads_or): with the
 // [run, NONE, run, NONE] pattern k_accumulate leaves, every second step.
 // ---------------------------------------------------------------------------
-static constexpr unsigned COOP_TREE_MAX = 16384;
 
 template<class FP>
 SPPARK_DEVFN void reduce_runs_coop_item(xyzz_mem<FP::N>* buckets, u32* out_key, xyzz_mem<FP::N>* out_pt,
@@ -243,8 +239,6 @@ namespace sppark_amd {
 // work-group of four waves per CU (<= COOP_LEVEL_MAX work items: MSMs of <= 2^16 points, and the last chunked level of
 // larger ones): the same running sums, every addition and doubling by four waves.  64 work items per work-group.
 // ---------------------------------------------------------------------------
-// (24576 or 32768 -- 1.5 or 2 rounds of work-groups -- change nothing measurable: profiles/r04_msm_coop_level_max.log)
-static constexpr unsigned COOP_LEVEL_MAX = 16384;
 
 template<class FP>
 __global__ __launch_bounds__(COOP_NT)
@@ -426,7 +420,6 @@ void k_piece_level_coop(xyzz_mem<FP::N>* __restrict__ buckets, u32* __restrict__
 // (the barrier's work-group-scope release / acquire: the records stay in global memory, same slots as the per-level form).
 // Same box, wall (profiles/r06_msm_piece_tail_ab.log): 2^10 0.426 -> 0.406 ms, 2^12 0.482 -> 0.463, 2^14 0.550 -> 0.541, 2^16 0.800 -> 0.788;
 // from 2^16 work items on the lane-per-addition launches are faster (2^14: 0.585 with the levels of 2^16 items in here).
-static constexpr size_t PIECE_FUSE_MAX = 32768;
 template<class FP>
 __global__ __launch_bounds__(COOP_NT, 2)         // (two work-groups per CU: 2^12 points are 512 work-groups)
 void k_piece_tail_coop(xyzz_mem<FP::N>* __restrict__ buckets, u32* rec_key, xyzz_mem<FP::N>* rec_pt,

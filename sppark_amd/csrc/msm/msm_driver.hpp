@@ -31,7 +31,7 @@
 #pragma once
 #include "msm_kernels.hpp"
 #include "msm_coop_kernels.hpp"
-#include "msm_plan.hpp"
+#include "msm_route.hpp"
 #include "../ec/jacobian_host.hpp"
 #include "../util/runtime.hpp"
 #include <algorithm>
@@ -62,10 +62,14 @@ public:
     static_assert(INTERNAL || sizeof(FH) == 4 * FD::N, "host and device coordinate fields must share the wire image");
     static constexpr size_t SCALAR_BYTES = sizeof(fr_d);
     static constexpr unsigned MAX_WINS = 128;
-    // one wave per SIMD on 256 CUs: bucket-sum grids up to this size run the paired-product one-wave kernels.  (Larger,
-    // work-bound grids are faster with the two-wave kernels: forcing the one-wave ones everywhere costs the tail of a
-    // 2^26-point MSM 2.0 ms and 0.5 ms at 2^24, profiles/r04_msm_lat_lanes_negative.log.)
-    static constexpr size_t LAT_LANES = 65536;
+    // what the route (msm_route.hpp) must know of the coordinate field
+    static msm_field field()
+    {
+        bool pairs_default = false;
+        if constexpr (G2_COOP_BUILT) pairs_default = fp_d::NL >= 14;
+        return msm_field{INTERNAL, MONTX, G2_COOP_BUILT, pairs_default, (unsigned)fp_d::N, (unsigned)sizeof(bucket_t), (unsigned)FP_BYTES,
+                         FRp::MOD, (unsigned)FRp::N};
+    }
     static constexpr size_t FIXED_BASE_MIN = (size_t)1 << 23;      // points from which set_points_fixed_base builds tables by itself
 
 private:
@@ -406,24 +410,30 @@ public:
     size_t preloaded() const { return pre_n; }
 
 private:
+    static void no_kernel() { HIP_OK(hipErrorInvalidDeviceFunction); }      // the route named a kernel this field does not have
+    // wire points -> the field's own records, by the kernel the route chooses (route_convert)
     void launch_convert(unsigned char* dst, const unsigned char* src, unsigned n, size_t stride, hipStream_t on = nullptr)
     {
+        if constexpr (INTERNAL)
+            issue_convert(route_convert(field(), tune.sw, n, stride, ((size_t)src & 15) == 0), dst, src, stride, on ? on : stream);
+    }
+    void issue_convert(const msm_step& s, unsigned char* dst, const unsigned char* src, size_t stride, hipStream_t on)
+    {
         if constexpr (INTERNAL) {
-            if (on == nullptr) on = stream;
-            unsigned grid = (n + 255) / 256;
-            // G1 points in either wire layout at a 16-byte-aligned base: the coalesced form (msm_kernels.hpp k_convert_points_staged)
-            if constexpr (MONTX) {
-                if ((stride == 2 * FP_BYTES || stride == 2 * FP_BYTES + 8) && ((size_t)src & 15) == 0 && tune.join != 6) {
-                    if (stride == 2 * FP_BYTES) hipLaunchKernelGGL((k_convert_points_staged<fp_d, false>), dim3(grid), dim3(256), 0, on, dst, src, n);
-                    else                        hipLaunchKernelGGL((k_convert_points_staged<fp_d, true>), dim3(grid), dim3(256), 0, on, dst, src, n);
-                    HIP_OK(hipGetLastError());
-                    return;
-                }
+            const dim3 grid(s.gx), block(s.block);
+            switch (s.kernel) {
+            case MK_CONVERT:         hipLaunchKernelGGL((k_convert_points<fp_d, false>), grid, block, 0, on, dst, src, s.count, (unsigned)stride); break;
+            case MK_CONVERT_FLAGGED: hipLaunchKernelGGL((k_convert_points<fp_d, true>), grid, block, 0, on, dst, src, s.count, (unsigned)stride); break;
+            case MK_CONVERT_STAGED:
+                if constexpr (MONTX) hipLaunchKernelGGL((k_convert_points_staged<fp_d, false>), grid, block, 0, on, dst, src, s.count); else no_kernel();
+                break;
+            case MK_CONVERT_STAGED_FLAGGED:
+                if constexpr (MONTX) hipLaunchKernelGGL((k_convert_points_staged<fp_d, true>), grid, block, 0, on, dst, src, s.count); else no_kernel();
+                break;
+            default: no_kernel();
             }
-            if (stride > 2 * FP_BYTES) hipLaunchKernelGGL((k_convert_points<fp_d, true>), dim3(grid), dim3(256), 0, on, dst, src, n, (unsigned)stride);
-            else                       hipLaunchKernelGGL((k_convert_points<fp_d, false>), dim3(grid), dim3(256), 0, on, dst, src, n, (unsigned)stride);
             HIP_OK(hipGetLastError());
-        }
+        } else no_kernel();
     }
 
     // points per chunk.  |stage_per_point|: bytes of host-resident input per point that have to be
@@ -566,13 +576,25 @@ private:
         HIP_OK(hipGetLastError());
     }
 
+    // The kernels between the sort and the copy of the window sums are what the ROUTE says (msm_route.hpp make_route): this
+    // function keeps the streams and events, the per-group sort and accumulation loop, the memsets and the copies.
     // |redo|: only the fan-in tree over the records the piece tree left, and everything after it (invoke(), when the flag of
     // the first pass says that a bucket had more pieces than the piece tree was sized for)
+    // (|may_defer|: the caller looks at the flag after this MSM -- invoke() with one chunk)
     void enqueue(const msm_plan& p, const layout& l, const unsigned char* d_points, size_t stride, bool preconverted,
                  const u32* d_scalars, bool mont, std_bucket_t* h_out, bool first_timed, unsigned fb_n = 0, unsigned fb_nwins = 0,
                  bool redo = false, bool may_defer = false)
     {
-        const bool flagged = !preconverted && stride > 2 * FP_BYTES;
+        msm_call call;
+        call.fb_n = fb_n; call.redo = redo; call.may_defer = may_defer;
+        call.convert = INTERNAL && !preconverted;
+        call.flagged = !preconverted && stride > 2 * FP_BYTES;
+        call.stride = stride; call.aligned16 = ((size_t)d_points & 15) == 0;
+#ifdef SPPARK_TUNING
+        if (const char* e = getenv("SPPARK_TOP_CUT")) call.top_cut = (unsigned)atoi(e);        // "sb sp" as two digits, e.g. 24 (sweeps only)
+#endif
+        const msm_route route = make_route(p, tune, field(), call);
+        if (route.overflow) HIP_OK(hipErrorInvalidValue);
         const bool multi = p.G > 1;
         if (multi) need_aux();
         if (timing && first_timed && !redo) { need_tev(2 + 2 * p.G); HIP_OK(hipEventRecord(tev[0], stream)); }
@@ -581,8 +603,111 @@ private:
             HIP_OK(hipStreamWaitEvent(aux, ev_fork, 0));
         }
         bucket_t* buckets = (bucket_t*)(blob + l.buckets);
-        u32* keyA = (u32*)(blob + l.keyA); bucket_t* ptA = (bucket_t*)(blob + l.ptA);
-        u32* keyB = (u32*)(blob + l.keyB); bucket_t* ptB = (bucket_t*)(blob + l.ptB);
+        std_bucket_t* fin = (std_bucket_t*)(blob + l.sums);
+        const u32* off0 = (const u32*)(blob + l.off[0]);
+        // the route's buffer roles as pointers
+        auto rec = [&](msm_buf b) -> bucket_t* {
+            switch (b) {
+            case MB_BUCKETS: return buckets;
+            case MB_PT_A: return (bucket_t*)(blob + l.ptA);
+            case MB_PT_B: return (bucket_t*)(blob + l.ptB);
+            case MB_A1: return (bucket_t*)(blob + l.A1);
+            case MB_W1: return (bucket_t*)(blob + l.W1);
+            case MB_A2: return (bucket_t*)(blob + l.A2);
+            case MB_W2: return (bucket_t*)(blob + l.W2);
+            default: return nullptr;
+            }
+        };
+        auto key = [&](msm_buf b) -> u32* {
+            return (u32*)(b == MB_KEY_A ? blob + l.keyA : b == MB_KEY_B ? blob + l.keyB : b == MB_KEY_C ? blob + l.keyC : nullptr);
+        };
+        auto flag_word = [&](msm_flag f) -> u32* { return f == MF_SCRATCH ? (u32*)(blob + l.flag) : f == MF_SMALL ? d_pflag : nullptr; };
+        // one step of the route: roles -> pointers, and the launch.  (|w0|, |wn|, |b|: the window group and sort set of an accumulation)
+        auto launch = [&](const msm_step& s, unsigned w0 = 0, unsigned wn = 0, unsigned b = 0) {
+            const dim3 grid(s.gx, s.gy), block(s.block);
+            bucket_t *r0 = rec(s.rd[0]), *r1 = rec(s.rd[1]), *w0p = rec(s.wr[0]), *w1p = rec(s.wr[1]);
+            u32* flag = flag_word(s.flag);
+            const u32* offp = multi ? (const u32*)nullptr : off0;       // (one group: empty buckets are recognised from the offsets)
+#define SPPARK_GO(kernel, ...) hipLaunchKernelGGL((kernel), grid, block, s.lds, stream, __VA_ARGS__)
+#define SPPARK_GO_G1(kernel, ...) do { if constexpr (MONTX) SPPARK_GO(kernel, __VA_ARGS__); else no_kernel(); } while (0)
+            switch (s.kernel) {
+            case MK_CONVERT: case MK_CONVERT_FLAGGED: case MK_CONVERT_STAGED: case MK_CONVERT_STAGED_FLAGGED:
+                issue_convert(s, blob + l.conv, d_points, stride, stream);
+                return;
+            // (fields with their own records read them at their own stride and ignore this one)
+            case MK_ACCUMULATE: case MK_ACCUMULATE_FLAGGED: case MK_ACCUMULATE_G2C: {
+                const u32* sorted = (const u32*)(blob + l.sorted[b]);
+                const u32* off = (const u32*)(blob + l.off[b]);
+                const dim3 rows(s.gx, wn);
+                u32* keyA = key(MB_KEY_A); bucket_t* ptA = rec(MB_PT_A);
+                if (s.kernel == MK_ACCUMULATE_G2C) {
+                    if constexpr (G2_COOP_BUILT)
+                        hipLaunchKernelGGL((k_accumulate_g2c<fp_d>), rows, block, 0, stream, buckets, keyA, ptA, d_points, (unsigned)stride,
+                                           sorted, off, p.n, p.NB, p.L, p.chunks_per_win, w0);
+                    else no_kernel();
+                } else if (s.kernel == MK_ACCUMULATE_FLAGGED)
+                    hipLaunchKernelGGL((k_accumulate<fp_d, true>), rows, block, 0, stream, buckets, keyA, ptA, d_points, (unsigned)stride,
+                                       sorted, off, p.n, p.NB, p.L, p.chunks_per_win, w0);
+                else
+                    hipLaunchKernelGGL((k_accumulate<fp_d, false>), rows, block, 0, stream, buckets, keyA, ptA, d_points, (unsigned)stride,
+                                       sorted, off, p.n, p.NB, p.L, p.chunks_per_win, w0);
+                break;
+            }
+            case MK_PIECE_LEVEL:
+                SPPARK_GO(k_piece_level<fp_d>, buckets, key(s.rd[0]), r1, off0, p.NB, p.L, p.chunks_per_win, p.nwins, route.piece_cmax, s.t, s.last, flag);
+                break;
+            case MK_PIECE_LEVEL_COOP:
+                SPPARK_GO_G1(k_piece_level_coop<fp_d>, buckets, key(s.rd[0]), r1, off0, p.NB, p.L, p.chunks_per_win, p.nwins, route.piece_cmax, s.t, s.last, flag);
+                break;
+            case MK_PIECE_TAIL_COOP:
+                SPPARK_GO_G1(k_piece_tail_coop<fp_d>, buckets, key(s.rd[0]), r1, off0, p.NB, p.L, p.chunks_per_win, p.nwins, route.piece_cmax, s.t, s.lgGB, flag);
+                break;
+            case MK_JOIN_RUNS:
+                HIP_OK(hipMemsetAsync(flag, 0, 4, stream));
+                SPPARK_GO(k_join_runs<fp_d>, buckets, key(s.wr[0]), key(s.rd[0]), r1, s.count, flag);
+                break;
+            case MK_REDUCE_RUNS:
+                SPPARK_GO(k_reduce_runs<fp_d>, buckets, key(s.wr[0]), w1p, key(s.rd[0]), r1, s.count, s.fan, s.nthreads, (int)s.last, (const u32*)flag);
+                break;
+            case MK_REDUCE_RUNS_COOP:
+                SPPARK_GO_G1(k_reduce_runs_coop<fp_d>, buckets, key(s.wr[0]), w1p, key(s.rd[0]), r1, s.count, s.fan, s.nthreads, 0, (const u32*)flag);
+                break;
+            case MK_REDUCE_TAIL:
+                SPPARK_GO(k_reduce_tail<fp_d>, buckets, key(s.rd[0]), r1, key(s.wr[0]), w1p, s.count, s.fan, (const u32*)flag);
+                break;
+            case MK_REDUCE_TAIL_COOP:
+                SPPARK_GO_G1(k_reduce_tail_coop<fp_d>, buckets, key(s.rd[0]), r1, key(s.wr[0]), w1p, s.count, s.fan, (const u32*)flag);
+                break;
+            case MK_BUCKET_SMALL_BITS_COOP: SPPARK_GO_G1(k_bucket_small_bits_coop<fp_d>, w0p, buckets, off0, p.NB, s.m); break;
+            case MK_BUCKET_LEVEL1:      SPPARK_GO(k_bucket_level1<fp_d>, w0p, w1p, buckets, p.NB, s.fan, p.nwins, offp); break;
+            case MK_BUCKET_LEVEL1_LAT:  SPPARK_GO_G1(k_bucket_level1_lat<fp_d>, w0p, w1p, buckets, p.NB, s.fan, p.nwins, offp); break;
+            case MK_BUCKET_LEVEL1_PIPE: SPPARK_GO_G1(k_bucket_level1_pipe<fp_d>, w0p, w1p, buckets, p.NB, s.fan, p.nwins, offp); break;
+            case MK_BUCKET_LEVEL1_COOP: SPPARK_GO_G1(k_bucket_level1_coop<fp_d>, w0p, w1p, buckets, p.NB, s.fan, p.nwins, offp); break;
+            case MK_BUCKET_LEVELN:      SPPARK_GO(k_bucket_levelN<fp_d>, w0p, w1p, r0, r1, s.count, s.fan, s.lgG, p.nwins); break;
+            case MK_BUCKET_LEVELN_LAT:  SPPARK_GO_G1(k_bucket_levelN_lat<fp_d>, w0p, w1p, r0, r1, s.count, s.fan, s.lgG, p.nwins); break;
+            case MK_BUCKET_LEVELN_PIPE: SPPARK_GO_G1(k_bucket_levelN_pipe<fp_d>, w0p, w1p, r0, r1, s.count, s.fan, s.lgG, p.nwins); break;
+            case MK_BUCKET_LEVELN_COOP: SPPARK_GO_G1(k_bucket_levelN_coop<fp_d>, w0p, w1p, r0, r1, s.count, s.fan, s.lgG, p.nwins); break;
+            case MK_BUCKET_TOP_BITS:
+                if (s.lds > 65536) lds_attr((const void*)k_bucket_top_bits<fp_d>, s.lds);
+                SPPARK_GO(k_bucket_top_bits<fp_d>, w0p, r0, r1, s.count, s.m, s.lgG);
+                break;
+            case MK_BUCKET_TOP_SUM: SPPARK_GO(k_bucket_top_sum<fp_d>, w0p, r0, s.m); break;
+            case MK_BUCKET_TOP_BITS_COOP:
+                if constexpr (MONTX) { if (s.lds > 65536) lds_attr((const void*)k_bucket_top_bits_coop<fp_d>, s.lds); }
+                SPPARK_GO_G1(k_bucket_top_bits_coop<fp_d>, w0p, r0, r1, s.count, s.m, s.lgG, s.sb, s.sp);
+                break;
+            case MK_BUCKET_TOP_SUM_COOP:        // (the wire image with it, and the small sizes' flag behind the sums)
+                SPPARK_GO_G1(k_bucket_top_sum_coop<fp_d>, w0p, r0, s.count, fin, flag, flag ? reinterpret_cast<u32*>(fin + p.nwins) : (u32*)nullptr);
+                break;
+            case MK_FINALIZE:
+                if constexpr (INTERNAL) SPPARK_GO((k_finalize<fp_d, STD_WORDS>), fin, r0, p.nwins); else no_kernel();
+                break;
+            default: no_kernel();
+            }
+#undef SPPARK_GO_G1
+#undef SPPARK_GO
+            HIP_OK(hipGetLastError());
+        };
         // With ONE window group the bucket offsets of every window are still there when the bucket sums run:
         // empty buckets are recognised from them and never read (k_bucket_level1), so no memset.  With several
         // groups the two offset sets are reused, and the buckets are cleared instead.
@@ -598,8 +723,8 @@ private:
                 // (the conversion does not depend on the scalars, but running it on the second stream beside the digit /
                 // sort kernels gains nothing: all of them are memory-bound and share HBM -- 13.4 ms before the accumulation
                 // either way at 2^26, profiles/r04_msm_convert_beside_sort_negative.log; round 2 measured the same)
-                if (INTERNAL && !preconverted) {    // wire points -> the field's own records (2 products per point)
-                    launch_convert(blob + l.conv, d_points, p.n, stride);
+                if (call.convert) {                 // wire points -> the field's own records (2 products per point)
+                    launch(route.steps[0]);
                     d_points = blob + l.conv;
                 }
             } else {
@@ -609,299 +734,43 @@ private:
                 HIP_OK(hipStreamWaitEvent(stream, ev_sorted[b], 0));
             }
             if (timing && first_timed) HIP_OK(hipEventRecord(tev[2 + 2 * g], stream));
-            {
-                const u32* sorted = (const u32*)(blob + l.sorted[b]);
-                const u32* off = (const u32*)(blob + l.off[b]);
-                dim3 grid((p.chunks_per_win + 255) / 256, wn);
-                // G2: one Fp2 component per wave (msm_g2c_kernels.hpp).  The default for the 14-limb base fields: BLS12-381 G2
-                // 2^22 47.8 -> 40.2 ms, 2^20 15.3 -> 14.0; NOT for the 10-limb one, whose whole Fp2 bucket fits a lane at two
-                // waves per SIMD already (alt_bn128 G2 2^22 21.6 -> 23.6 ms); profiles/r05_g2_coop_ab.log.
-                // tune.g2_coop: 0 = that rule, 1 = wave pairs, 2 = one lane per addition (sppark_msm_g2_path).
-                bool by_pairs = false;
-                if constexpr (G2_COOP_BUILT) {
-                    if (tune.g2_coop == 1 || (tune.g2_coop == 0 && fp_d::NL >= 14)) {
-                        by_pairs = true;
-                        dim3 grid2((p.chunks_per_win + 63) / 64, wn);
-                        hipLaunchKernelGGL((k_accumulate_g2c<fp_d>), grid2, dim3(G2C_NT), 0, stream,
-                                           buckets, keyA, ptA, d_points, (unsigned)stride, sorted, off,
-                                           p.n, p.NB, p.L, p.chunks_per_win, w0);
-                    }
-                }
-                // (fields with their own records read them at their own stride and ignore this one)
-                if (by_pairs) {}
-                else if (flagged)
-                    hipLaunchKernelGGL((k_accumulate<fp_d, true>), grid, dim3(256), 0, stream,
-                                       buckets, keyA, ptA, d_points, (unsigned)stride, sorted, off,
-                                       p.n, p.NB, p.L, p.chunks_per_win, w0);
-                else
-                    hipLaunchKernelGGL((k_accumulate<fp_d, false>), grid, dim3(256), 0, stream,
-                                       buckets, keyA, ptA, d_points, (unsigned)stride, sorted, off,
-                                       p.n, p.NB, p.L, p.chunks_per_win, w0);
-                HIP_OK(hipGetLastError());
-            }
+            launch(route.steps[route.front - 1], w0, wn, b);
             if (timing && first_timed) HIP_OK(hipEventRecord(tev[3 + 2 * g], stream));
             if (multi) HIP_OK(hipEventRecord(ev_accdone[b], stream));
         }
 
-        // ---- small MSMs: the pieces of every bucket by a tree over the bucket's own pieces (msm_piece_kernels.hpp) ----
-        // Where a bucket is cut into MORE runs than k_join_runs walks (n / NB > 4 L: up to 2^16 points), log2(cmax) launches of
-        // one addition each replace the fan-in tree's eleven of up to three (2^16: 0.29 -> 0.09 ms, 2^12: 0.20 -> 0.08).  A
-        // bucket with more than cmax pieces (skewed scalars) keeps its records and raises the flag; the fan-in tree is NOT
-        // queued behind it -- ten launches that find nothing to do are 50 us -- but run afterwards by invoke() when the flag,
-        // which comes back with the window sums, is set.  (One window group, whose offsets are all still there.)
-        // (|may_defer|: the caller looks at the flag after this MSM -- invoke() with one chunk)
-        const unsigned piece_cm = may_defer ? piece_tree_cmax(p, multi, fb_n) : 0;
-        piece_pending = false;
-        // windows of up to 256 buckets (MSMs of up to 2^16 points): the subset sums straight from the buckets, then the parts of a
-        // window (msm_coop_kernels.hpp k_bucket_small_bits_coop); needs the offsets of every window: one window group
-        bool small_sums = false;
-        if constexpr (MONTX)
-            small_sums = !multi && fb_n == 0 && p.NB <= SMALL_SUMS_MAX_NB && p.NB >= 2 && tune.K1 == 0 && tune.top == 0 && tune.K == 0
-                         && tune.join != 3 && tune.join != 4;
-        // The flag of the piece tree on that path costs no launch of its own: it lives in a word that is ZERO between MSMs
-        // (no memset), and the last kernel of the path -- k_bucket_top_sum_coop, which writes the window sums' wire image --
-        // puts it behind the sums (one copy brings both to the host) and clears it.  (2^12: a 5 us fill with a 6 us gap in front
-        // of the levels and a 5 us copy behind them, of a 0.39 ms MSM.)  Other paths: memset, levels, a copy of their own.
-        bool flag_with_sums = false;
-        if constexpr (MONTX) flag_with_sums = small_sums && (piece_cm != 0 || redo);
-        if (flag_with_sums && !d_pflag) {
+        // ---- the tail: [piece tree |] record tree, bucket sums -- msm_route.hpp says which, and why ----
+        unsigned si = route.front;
+        piece_pending = route.piece_pending;
+        if (route.flag_with_sums && !d_pflag) {
             HIP_OK(hipMalloc((void**)&d_pflag, 64));
             HIP_OK(hipMemsetAsync(d_pflag, 0, 64, stream));
         }
-        if (piece_cm && !redo) {
-            u32* flag = flag_with_sums ? d_pflag : (u32*)(blob + l.flag);
-            if (!flag_with_sums) HIP_OK(hipMemsetAsync(flag, 0, 4, stream));
-            const u32* off = (const u32*)(blob + l.off[0]);
-            // the levels of few work items in one launch (k_piece_tail_coop; tune.join 8: every level a launch, 16 + x: from 2^x items)
-            unsigned t_fused = ~0u;
-            if constexpr (MONTX) if (tune.join != 4 && tune.join != 8)
-                t_fused = piece_tail_t0((size_t)p.nwins * p.NB, piece_cm, tune.join >= 16 ? (size_t)1 << (tune.join - 16) : PIECE_FUSE_MAX);
-            for (unsigned t = 0; (piece_cm >> (t + 1)) >= 1; t++) {
-                const unsigned last = (piece_cm >> (t + 2)) == 0;
-                const size_t nthr = (size_t)p.nwins * p.NB * (piece_cm >> (t + 1));
-                if constexpr (MONTX) if (t == t_fused) {
-                    const unsigned lgGB = piece_tail_lgGB(piece_cm, t);
-                    const size_t nwg = (((size_t)p.nwins * p.NB) + ((size_t)1 << lgGB) - 1) >> lgGB;
-                    hipLaunchKernelGGL(k_piece_tail_coop<fp_d>, dim3((unsigned)nwg), dim3(COOP_NT), 0, stream,
-                                       buckets, keyA, ptA, off, p.NB, p.L, p.chunks_per_win, p.nwins, piece_cm, t, lgGB, flag);
-                    HIP_OK(hipGetLastError());
-                    break;
-                }
-                bool coop = false;
-                if constexpr (MONTX) coop = nthr <= COOP_LEVEL_MAX && tune.join != 4;
-                if constexpr (MONTX) {
-                    if (coop) hipLaunchKernelGGL(k_piece_level_coop<fp_d>, dim3((unsigned)((nthr + 63) / 64)), dim3(COOP_NT), 0, stream,
-                                                 buckets, keyA, ptA, off, p.NB, p.L, p.chunks_per_win, p.nwins, piece_cm, t, last, flag);
-                }
-                if (!coop) hipLaunchKernelGGL(k_piece_level<fp_d>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream,
-                                              buckets, keyA, ptA, off, p.NB, p.L, p.chunks_per_win, p.nwins, piece_cm, t, last, flag);
-                HIP_OK(hipGetLastError());
-            }
+        if (route.pieces) {
+            // the flag word the piece steps raise: the scratch blob's is cleared here and copied back on its own; the small
+            // sizes' is zero already and comes back behind the window sums
+            const msm_flag which = route.steps[si].flag;
+            u32* flag = flag_word(which);
+            if (which == MF_SCRATCH) HIP_OK(hipMemsetAsync(flag, 0, 4, stream));
+            for (const unsigned end = si + route.pieces; si < end; si++) launch(route.steps[si]);
             if (!h_flag) HIP_OK(hipHostMalloc((void**)&h_flag, 64, hipHostMallocDefault));
-            if (!flag_with_sums) HIP_OK(hipMemcpyAsync(h_flag, flag, 4, hipMemcpyDeviceToHost, stream));
-            h_flag_cur = flag_with_sums ? reinterpret_cast<const u32*>(h_out + p.nwins) : h_flag;
-            piece_pending = true;
+            if (which == MF_SCRATCH) HIP_OK(hipMemcpyAsync(h_flag, flag, 4, hipMemcpyDeviceToHost, stream));
+            h_flag_cur = which == MF_SMALL ? reinterpret_cast<const u32*>(h_out + p.nwins) : h_flag;
         }
-        // ---- segmented record tree over the records of all windows -----------------------------
-        if (!piece_pending) {
-            size_t nrec = (size_t)2 * p.nwins * p.chunks_per_win;
-            u32* ik = keyA; bucket_t* ip = ptA; u32* ok = keyB; bucket_t* op = ptB;
-            // segments of <= JOIN_WALK records (with uniform scalars: all of them) in one launch; the tree
-            // below then only sees the records of longer segments and returns at once when there are none
-            const u32* skip = nullptr;
-            // (not when the average bucket is longer than four runs: every segment is then longer than the join's walk
-            // and the launch finds nothing to do -- below ~2^19 points)
-            if (tune.join != 1 && !redo && (size_t)p.n / p.NB <= (size_t)4 * p.L) {
-                u32* keyC = (u32*)(blob + l.keyC); u32* flag = (u32*)(blob + l.flag);
-                HIP_OK(hipMemsetAsync(flag, 0, 4, stream));
-                const size_t nthr = nrec / 2 + 1;
-                hipLaunchKernelGGL(k_join_runs<fp_d>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream,
-                                   buckets, keyC, keyA, ptA, (unsigned)nrec, flag);
-                HIP_OK(hipGetLastError());
-                ik = keyC; skip = flag;
-            }
-            bool coop_tree = false;
-            if constexpr (MONTX) coop_tree = tune.join != 4 && tune.join != 2;
-            for (;;) {
-                unsigned nthreads = (unsigned)((nrec + p.F - 1) / p.F);
-                if constexpr (MONTX) {
-                    // from one work-group per CU on: four waves per addition (msm_coop_kernels.hpp)
-                    if (coop_tree && nthreads <= 64) {
-                        hipLaunchKernelGGL(k_reduce_tail_coop<fp_d>, dim3(1), dim3(COOP_NT), 0, stream,
-                                           buckets, ik, ip, ok, op, (unsigned)nrec, p.F, skip);
-                        HIP_OK(hipGetLastError());
-                        break;
-                    }
-                    if (coop_tree && nthreads <= COOP_TREE_MAX) {
-                        hipLaunchKernelGGL(k_reduce_runs_coop<fp_d>, dim3((nthreads + 63) / 64), dim3(COOP_NT), 0, stream,
-                                           buckets, ok, op, ik, ip, (unsigned)nrec, p.F, nthreads, 0, skip);
-                        HIP_OK(hipGetLastError());
-                        nrec = (size_t)2 * nthreads;
-                        std::swap(ik, ok); std::swap(ip, op);
-                        continue;
-                    }
-                }
-                if (nthreads <= REDUCE_TAIL_NT && tune.join != 2) {     // the narrow end: every remaining level in one launch
-                    // (the level kernels write into the OTHER buffer pair; here the pairs alternate from |ik| on)
-                    hipLaunchKernelGGL(k_reduce_tail<fp_d>, dim3(1), dim3(REDUCE_TAIL_NT), 0, stream,
-                                       buckets, ik, ip, ok, op, (unsigned)nrec, p.F, skip);
-                    HIP_OK(hipGetLastError());
-                    break;
-                }
-                int last = nthreads == 1;
-                hipLaunchKernelGGL(k_reduce_runs<fp_d>, dim3((nthreads + 255) / 256), dim3(256), 0, stream,
-                                   buckets, ok, op, ik, ip, (unsigned)nrec, p.F, nthreads, last, skip);
-                HIP_OK(hipGetLastError());
-                if (last) break;
-                nrec = (size_t)2 * nthreads;
-                std::swap(ik, ok); std::swap(ip, op);
-            }
-        }
-        // ---- per-window weighted bucket sums ----------------------------------------------------
-        bucket_t* A1 = (bucket_t*)(blob + l.A1); bucket_t* W1 = (bucket_t*)(blob + l.W1);
-        bucket_t* A2 = (bucket_t*)(blob + l.A2); bucket_t* W2 = (bucket_t*)(blob + l.W2);
-        bucket_t* result;
-        bool finalized = false;
-        if constexpr (MONTX) {
-            if (small_sums) {
-                const unsigned m = lg2_floor(p.NB);
-                hipLaunchKernelGGL(k_bucket_small_bits_coop<fp_d>, dim3(m + 1, p.nwins), dim3(COOP_NT), 0, stream,
-                                   A2, buckets, (const u32*)(blob + l.off[0]), p.NB, m);
-                HIP_OK(hipGetLastError());
-                std_bucket_t* fin = (std_bucket_t*)(blob + l.sums);
-                hipLaunchKernelGGL(k_bucket_top_sum_coop<fp_d>, dim3(p.nwins), dim3(COOP_NT), 0, stream, W2, A2, m + 1,
-                                   fin,                                         // (the wire image with it: no k_finalize)
-                                   flag_with_sums ? d_pflag : (u32*)nullptr, flag_with_sums ? reinterpret_cast<u32*>(fin + p.nwins) : (u32*)nullptr);
-                HIP_OK(hipGetLastError());
-                result = W2; finalized = true;
-            }
-        }
-        if (!small_sums) {
-            unsigned nitems = p.NB / p.K1;
-            size_t nthr = (size_t)p.nwins * nitems;
-            // grids of at most one resident round (one wave per SIMD: 65 536 lanes) are chains of dependent additions:
-            // the _lat kernels (no register cap, products in pairs); larger ones are work: two waves per SIMD
-            const u32* offp = multi ? (const u32*)nullptr : (const u32*)(blob + l.off[0]);
-            bool lat = false;
-            if constexpr (MONTX) lat = nthr <= LAT_LANES && tune.join != 3;
-            if constexpr (MONTX) {
-                // (at most one work-group of four waves per CU: four waves per operation, msm_coop_kernels.hpp)
-                if (lat && nthr <= COOP_LEVEL_MAX && tune.join != 4)
-                    hipLaunchKernelGGL(k_bucket_level1_coop<fp_d>, dim3((unsigned)((nthr + 63) / 64)), dim3(COOP_NT), 0, stream,
-                                       A1, W1, buckets, p.NB, p.K1, p.nwins, offp);
-                // (between that and one resident round of waves: the two chains of a work item on two waves; tune.join 10: on one)
-                else if (lat && tune.join != 10 && tune.join != 4)
-                    hipLaunchKernelGGL(k_bucket_level1_pipe<fp_d>, dim3((unsigned)((nthr + 63) / 64)), dim3(128), 0, stream,
-                                       A1, W1, buckets, p.NB, p.K1, p.nwins, offp);
-                else if (lat) hipLaunchKernelGGL(k_bucket_level1_lat<fp_d>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream,
-                                                 A1, W1, buckets, p.NB, p.K1, p.nwins, offp);
-            }
-            if (!lat) hipLaunchKernelGGL(k_bucket_level1<fp_d>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream,
-                                         A1, W1, buckets, p.NB, p.K1, p.nwins, offp);
-            HIP_OK(hipGetLastError());
-            unsigned lgG = lg2_floor(p.K1);
-            bucket_t *ia = A1, *iw = W1, *oa = A2, *ow = W2;
-            while (nitems > 1) {
-                // the top of the sums by bit-weighted subset sums (msm_kernels.hpp k_bucket_top_bits): depth, not work
-                if (nitems <= (tune.top ? tune.top : BUCKET_TOP_MAX) && nitems >= 32 && (nitems & (nitems - 1)) == 0
-                    && (size_t)p.NB / p.K1 >= 32) {
-                    const unsigned m = lg2_floor(nitems);
-                    bool coop = false;
-                    if constexpr (MONTX) coop = tune.join != 4;     // (4: the one-wave-per-operation kernels, A/B switch)
-                    if constexpr (MONTX) {
-                        if (coop) {
-                            // the tree and the doubling chains by four waves per operation (msm_coop_kernels.hpp)
-                            // (a work-group per PIECE of a sum: msm_kernels.hpp bucket_top_piece; join == 7: per sum, the A/B switch)
-                            unsigned sb = 1, sp = 1;
-                            if (tune.join != 7) bucket_top_cut(nitems, COOP_NT, sb, sp);
-#ifdef SPPARK_TUNING
-                            if (const char* e = getenv("SPPARK_TOP_CUT")) {         // "sb sp" as two digits, e.g. 24 (sweeps only)
-                                const unsigned v = (unsigned)atoi(e), s1 = v / 10, s2 = v % 10;
-                                if (s1 >= 1 && s2 >= 1 && m * s1 + s2 <= 32 && nitems >= COOP_NT * s2) { sb = s1; sp = s2; }
-                            }
-#endif
-                            const size_t lds = top_bits_coop_lds(fp_d::N);
-                            if (lds > 65536) lds_attr((const void*)k_bucket_top_bits_coop<fp_d>, lds);
-                            hipLaunchKernelGGL(k_bucket_top_bits_coop<fp_d>, dim3(m * sb + sp, p.nwins), dim3(COOP_NT), lds, stream,
-                                               oa, ia, iw, nitems, m, lgG, sb, sp);
-                            HIP_OK(hipGetLastError());
-                            hipLaunchKernelGGL(k_bucket_top_sum_coop<fp_d>, dim3(p.nwins), dim3(COOP_NT), 0, stream, ow, oa, m * sb + sp,
-                                               (std_bucket_t*)(blob + l.sums),             // (the wire image with it: no k_finalize)
-                                               (u32*)nullptr, (u32*)nullptr);
-                            HIP_OK(hipGetLastError());
-                            finalized = true;
-                        }
-                    }
-                    if (!coop) {
-                        const size_t img = (size_t)BUCKET_TOP_NT * sizeof(bucket_t);
-                        if (img > 65536)
-                            lds_attr((const void*)k_bucket_top_bits<fp_d>, img);
-                        hipLaunchKernelGGL(k_bucket_top_bits<fp_d>, dim3(m + 1, p.nwins), dim3(BUCKET_TOP_NT), img, stream,
-                                           oa, ia, iw, nitems, m, lgG);
-                        HIP_OK(hipGetLastError());
-                        hipLaunchKernelGGL(k_bucket_top_sum<fp_d>, dim3(p.nwins), dim3(32), 32 * sizeof(bucket_t), stream, ow, oa, m);
-                        HIP_OK(hipGetLastError());
-                    }
-                    std::swap(iw, ow);
-                    break;
-                }
-                unsigned K = std::min(p.K, nitems);
-                nthr = (size_t)p.nwins * (nitems / K);
-                lat = false;
-                if constexpr (MONTX) lat = nthr <= LAT_LANES && tune.join != 3;
-                if constexpr (MONTX) {
-                    if (lat && nthr <= COOP_LEVEL_MAX && tune.join != 4)
-                        hipLaunchKernelGGL(k_bucket_levelN_coop<fp_d>, dim3((unsigned)((nthr + 63) / 64)), dim3(COOP_NT), 0, stream,
-                                           oa, ow, ia, iw, nitems, K, lgG, p.nwins);
-                    else if (lat && tune.join != 10 && tune.join != 4)      // (its three sums on three waves; tune.join 10: on one lane)
-                        hipLaunchKernelGGL(k_bucket_levelN_pipe<fp_d>, dim3((unsigned)((nthr + 63) / 64)), dim3(192), 0, stream,
-                                           oa, ow, ia, iw, nitems, K, lgG, p.nwins);
-                    else if (lat) hipLaunchKernelGGL(k_bucket_levelN_lat<fp_d>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream,
-                                                     oa, ow, ia, iw, nitems, K, lgG, p.nwins);
-                }
-                if (!lat) hipLaunchKernelGGL(k_bucket_levelN<fp_d>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream,
-                                             oa, ow, ia, iw, nitems, K, lgG, p.nwins);
-                HIP_OK(hipGetLastError());
-                nitems /= K; lgG += lg2_floor(K);
-                std::swap(ia, oa); std::swap(iw, ow);
-            }
-            result = iw;
-        }
+        for (; si < route.nsteps && route.steps[si].kernel != MK_FINALIZE; si++) launch(route.steps[si]);
         if (timing && first_timed && !redo) HIP_OK(hipEventRecord(tev[1], stream));
         // ---- device -> host: one XYZZ per window (wire image); Horner on the host ------------------
         if constexpr (INTERNAL) {
-            std_bucket_t* fin = (std_bucket_t*)(blob + l.sums);
-            if (!finalized) {
-                hipLaunchKernelGGL((k_finalize<fp_d, STD_WORDS>), dim3((p.nwins + 63) / 64), dim3(64), 0, stream, fin, result, p.nwins);
-                HIP_OK(hipGetLastError());
-            }
-            HIP_OK(hipMemcpyAsync(h_out, fin, (p.nwins + (flag_with_sums ? 1 : 0)) * sizeof(std_bucket_t), hipMemcpyDeviceToHost, stream));
+            if (si < route.nsteps) launch(route.steps[si]);         // k_finalize, where no step wrote the wire image
+            HIP_OK(hipMemcpyAsync(h_out, fin, (p.nwins + (route.flag_with_sums ? 1 : 0)) * sizeof(std_bucket_t), hipMemcpyDeviceToHost, stream));
         } else {
-            HIP_OK(hipMemcpyAsync(h_out, result, p.nwins * sizeof(std_bucket_t), hipMemcpyDeviceToHost, stream));
+            HIP_OK(hipMemcpyAsync(h_out, rec(route.result), p.nwins * sizeof(std_bucket_t), hipMemcpyDeviceToHost, stream));
         }
     }
 
 public:
-    // pieces per bucket the piece tree of a small MSM takes, 0 = the record list goes through k_join_runs / the fan-in tree:
-    // one window group, not the fixed-base window, buckets longer than the join's walk, at most 2^10 pieces
-    // (tune.join 5: never -- the A/B switch)
-    unsigned piece_tree_cmax(const msm_plan& p, bool multi, unsigned fb_n) const
-    {
-        if (multi || fb_n || tune.join == 5 || tune.join == 1) return 0;
-        if ((size_t)p.n / p.NB <= (size_t)4 * p.L) return 0;
-        // The TOP window is not uniform even for uniform scalars: the recoding folds s > r/2 to r - s, so its digit is at most
-        // (r/2) >> off_top and each of its buckets holds n 2^off_top / (r/2) entries -- BLS12-377's r = 0x12ab... in 4-bit
-        // windows: 0.43 n in one bucket against the average n / 8.  The tree is sized for that bucket too (the other short
-        // windows at the top are at most twice the average: within piece_cmax's head-room).
-        const unsigned off_top = p.nbits - window_len(p.nwins - 1, p.nwins, p.nbits);
-        long double r = 0;
-        for (int i = FRp::N - 1; i >= 0; i--) r = r * 4294967296.0L + (long double)FRp::MOD[i];
-        long double frac = ldexpl(1.0L, (int)off_top) / (r / 2);
-        if (frac > 1.0L) frac = 1.0L;
-        const size_t top_pieces = (size_t)((long double)p.n * frac / p.L) + 2;
-        const unsigned c = std::max(piece_cmax((size_t)p.n / p.NB / p.L + 1), piece_cmax_exact(top_pieces + top_pieces / 4 + 4));
-        return c <= 1024 ? c : 0;
-    }
+    // pieces per bucket the piece tree of a small MSM takes (msm_route.hpp piece_tree_cmax), 0 = none
+    unsigned piece_tree_cmax(const msm_plan& p) const { return sppark_amd::piece_tree_cmax(p, tune.sw, 0, FRp::MOD, (unsigned)FRp::N); }
 private:
 
     // Horner over the window sums (the reference's host-side collect, pippenger.cuh:627-727, is O(256 * windows))

@@ -68,7 +68,7 @@ SPPARK_DEVFN void accumulate_chunk_g2c(xyzz_mem<F2::N>* buckets, u32* rec_key, x
     else           { acc.store(&rec_pt[rec0 + 1], role); if (role == 0) { rec_key[rec0] = slot0_key; rec_key[rec0 + 1] = key; } }
 }
 
-static constexpr unsigned G2C_NT = 128;             // a pair of waves
+// (G2C_NT = 128 lanes, a pair of waves: msm_thresholds.hpp)
 // (the converted records carry their own infinity flag: one instantiation serves both wire layouts)
 template<class F2>
 __global__ __launch_bounds__(128, 2)

@@ -29,6 +29,7 @@
 #pragma once
 #include "../ec/xyzz_dev.hpp"
 #include "../ec/xyzzx_dev.hpp"
+#include "msm_thresholds.hpp"
 
 namespace sppark_amd {
 
@@ -51,8 +52,7 @@ static constexpr u32 KEY_NONE = 0xffffffffu;
 // its short top window with an lshift trick instead, sort.cuh:92,111,339).
 // Output word: bit31 = sign, low bits = |digit|, 0 = no contribution.
 // |limb(k)| returns 32-bit limb k of the reduced magnitude (k <= N, limb N = 0).
-__host__ __device__ inline unsigned window_len(unsigned w, unsigned nwins, unsigned nbits)   // also used by the host Horner
-{   return nbits / nwins + (w < nbits % nwins ? 1u : 0u);   }
+// (window_len: msm_thresholds.hpp)
 
 // Only the digits of windows [w_begin, w_begin + w_count) are stored (a window group of the
 // pipelined driver), at digits[(w - w_begin) * n + i]; the carry still runs through all
@@ -422,10 +422,7 @@ void k_reduce_runs(xyzz_mem<FP::N>* __restrict__ buckets,
 // the remaining levels with a barrier between them (a launch boundary costs ~6 us, and below 2^18 points, where the
 // buckets are longer than the join's walk, nine of these levels are real work of one addition each).  Record buffers
 // ping-pong as in the launch-per-level loop; |buf0| holds the input of the first level run here.
-// (256 lanes = one wave per SIMD, like the other cold kernels: a 1024-lane work-group would cap the kernel at 128
-// registers -- 187 spilled for the 14-limb field, 3x slower per addition -- and, over Fp2, call the outlined addition,
-// which is compiled for up to 512, from a kernel that owns 128: that build hung the G2 tests)
-static constexpr unsigned REDUCE_TAIL_NT = 256;
+// (REDUCE_TAIL_NT = 256 lanes, and why not more: msm_thresholds.hpp)
 template<class FP>
 __global__ __launch_bounds__(REDUCE_TAIL_NT)
 void k_reduce_tail(xyzz_mem<FP::N>* __restrict__ buckets, u32* key0, xyzz_mem<FP::N>* pt0, u32* key1, xyzz_mem<FP::N>* pt1,
@@ -597,7 +594,7 @@ void k_bucket_levelN_lat(xyzz_mem<FP::N>* __restrict__ A2, xyzz_mem<FP::N>* __re
 // parts of a window with a 4..5-step tree.  m*M/2 + M additions instead of ~3M, at a depth of
 // ~M/512 + 8 + (m + lgG) doublings + 5 instead of (m/3) * (23 additions + doublings).
 // ---------------------------------------------------------------------------
-static constexpr unsigned BUCKET_TOP_MAX = 4096, BUCKET_TOP_NT = 256;
+// (BUCKET_TOP_MAX, BUCKET_TOP_NT: msm_thresholds.hpp)
 
 template<class FP>
 SPPARK_DEVFN void lds_tree_sum(xyzz_dev<FP>& acc, xyzz_mem<FP::N>* img, unsigned tid, unsigned nt)
@@ -655,17 +652,7 @@ SPPARK_DEVFN top_piece bucket_top_piece(unsigned q, unsigned m, unsigned sb, uns
     else            { t.b = m; t.sub = q - m * sb; t.nsub = sp; }
     return t;
 }
-// pieces per subset sum (sb) and per plain sum (sp) for |nitems| items and work-groups of |nt| lanes.  Measured
-// (profiles/r06_msm_top_cut_sweep.log, 2^18 .. 2^24 points): cutting the PLAIN sum of a 4096-item top in two -- the one
-// work-group with twice the additions per lane of all the others -- is the whole gain (tail 2^19 0.79 -> 0.72 ms, 2^20
-// 0.99 -> 0.94, 2^21 1.24 -> 1.16, 2^22 1.35 -> 1.30); more pieces (2 / 4, 2 / 8: twice the work-groups, two per CU) bring
-// nothing further -- what is left is the tree and the doublings -- and at 2048 items (2^18 points) nothing changes.
-// At most 32 parts per window (k_bucket_top_sum_coop's image).
-static inline void bucket_top_cut(unsigned nitems, unsigned nt, unsigned& sb, unsigned& sp)
-{
-    sb = 1;
-    sp = nitems >= 16 * nt ? 2 : 1;
-}
+// (pieces per subset sum and per plain sum: bucket_top_cut, msm_thresholds.hpp)
 
 template<class FP>
 SPPARK_DEVFN xyzz_dev<FP> bucket_top_sum_gather(const xyzz_mem<FP::N>* parts, unsigned m, unsigned w, unsigned tid)
@@ -675,8 +662,8 @@ SPPARK_DEVFN xyzz_dev<FP> bucket_top_sum_gather(const xyzz_mem<FP::N>* parts, un
     return acc;
 }
 
-// the small windows' form of the same sum, straight from the buckets (k_bucket_small_bits_coop, msm_coop_kernels.hpp)
-static constexpr unsigned SMALL_SUMS_MAX_NB = 256;
+// the small windows' form of the same sum, straight from the buckets (k_bucket_small_bits_coop, msm_coop_kernels.hpp):
+// windows of up to SMALL_SUMS_MAX_NB buckets (msm_thresholds.hpp)
 // the t-th (0-based) bucket NUMBER in 1 .. NB with bit b set; b == m: NB itself
 SPPARK_DEVFN unsigned small_sums_member(unsigned b, unsigned m, unsigned t)
 {   return b >= m ? (1u << m) : ((((t >> b) << 1) | 1u) << b) | (t & ((1u << b) - 1u));   }

@@ -86,25 +86,7 @@ SPPARK_DEVFN piece_job piece_job_of(u32* rec_key, const u32* off, unsigned NB, u
     return piece_job_bm(rec_key, off, NB, L, chunks_per_win, cmax, t, last, any_long, id % nb, (unsigned)(id / nb));
 }
 
-// The narrow end of the tree in ONE launch (k_piece_tail_coop): every level from t0 on, a work-group owning 2^lgGB buckets
-// with ALL their pairs, so that a level only waits for the work-group's own stores.  Work item |idx| of work-group |wg| at
-// level t: bucket (wg << lgGB) + idx % 2^lgGB, pair idx >> lgGB.  lgGB fills the 64 lanes of a cooperative addition at
-// level t0: 2^lgGB (cmax >> (t0 + 1)) >= 64 where the buckets allow.
-static inline unsigned piece_tail_lgGB(unsigned cmax, unsigned t0)
-{
-    const unsigned pm = cmax >> (t0 + 1);
-    unsigned lg = 0;
-    while ((pm << lg) < 64) lg++;
-    return lg;
-}
-// first level of the one-launch end: the first whose work items (buckets x pair slots) are at most |fuse_max|; the levels
-// before it are launches of their own (lane-per-addition kernels: throughput, not latency)
-static inline unsigned piece_tail_t0(size_t nbuckets, unsigned cmax, size_t fuse_max)
-{
-    unsigned t = 0;
-    while ((cmax >> (t + 1)) >= 1 && nbuckets * (cmax >> (t + 1)) > fuse_max) t++;
-    return t;
-}
+// (the one-launch narrow end's geometry -- piece_tail_lgGB, piece_tail_t0 -- and the tree's size piece_cmax: msm_thresholds.hpp)
 
 template<class FP>
 SPPARK_DEVFN void piece_apply(xyzz_mem<FP::N>* buckets, xyzz_mem<FP::N>* rec_pt, const piece_job& j)
@@ -132,17 +114,5 @@ void k_piece_level(xyzz_mem<FP::N>* __restrict__ buckets, u32* __restrict__ rec_
     piece_level_item<FP>(buckets, rec_key, rec_pt, off, NB, L, chunks_per_win, nwins, cmax, t, last, any_long,
                          (size_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
-
-// CMAX for an average bucket of |avg_pieces| pieces: a power of two >= 3 x + 4.  (Uniform scalars are NOT uniform digits in
-// the top window: it is a bit shorter than the others when the scalar bits do not divide evenly, and the modulus cuts its
-// range -- BLS12-381's r = 0x73ed... leaves 115 of the 128 values of a 7-bit top window, all of magnitude <= 64: 2.2 x the
-// entries per bucket.  The extra levels are launches of a few lanes that find nothing to add.)
-static inline unsigned piece_cmax_exact(size_t want)            // the power of two >= want
-{
-    unsigned c = 2;
-    while (c < want && c < 4096) c <<= 1;
-    return c;
-}
-static inline unsigned piece_cmax(size_t avg_pieces) { return piece_cmax_exact(3 * avg_pieces + 4); }
 
 } // namespace sppark_amd

@@ -1,11 +1,64 @@
 // The plan of an MSM -- window size, split of the bucket index between the two sort levels, run length, fan-ins --
-// as a function of the point count and the tunables.  Host logic only (no HIP): msm_driver.hpp launches what it says,
-// tests/emu/emu_plan.cpp checks its invariants over every size in the GPU-less container.
+// as a function of the point count and the tunables.  Host logic only (no HIP): msm_route.hpp turns it into the sequence
+// of launches, msm_driver.hpp issues them, tests/emu/emu_plan.cpp checks both over every size without a GPU.
 #pragma once
+#include "msm_thresholds.hpp"
 #include <algorithm>
 #include <cstddef>
 
 namespace sppark_amd {
+
+// The A/B switches of the tail: what sppark_msm_tune_tail's numeric code (and SPPARK_G2_JOIN in tuning builds) selects.
+// All false = what ships.  Each keeps an older form of one step reachable so that the two can be measured against each
+// other and tested against the oracle; msm_route.hpp reads them, nothing else does.
+struct msm_switches {
+    bool no_join = false;               // no k_join_runs: every record segment through the fan-in tree (fan-in 4, not 16)
+    bool no_narrow_end = false;         // a launch per level of the record tree: no k_reduce_tail, no cooperative tree kernels
+    bool no_latency_sums = false;       // bucket sums: the two-wave kernels at every grid size; no small windows' sums
+    bool no_coop = false;               // no four-waves-per-operation kernel anywhere (nor the two- / three-wave bucket sums)
+    bool no_piece_tree = false;         // small MSMs: the record list through the fan-in tree
+    bool convert_per_lane = false;      // point conversion: k_convert_points also where the staged form applies
+    bool top_per_sum = false;           // subset-sum top: a work-group per sum, not per piece
+    bool piece_level_launches = false;  // piece tree: every level a launch (no k_piece_tail_coop)
+    bool sums_one_lane = false;         // bucket sums between the cooperative grids and LAT_LANES: one lane per work item, not two / three waves
+    size_t piece_fuse_max = PIECE_FUSE_MAX;     // piece tree: levels of at most this many work items go into the one-launch end
+};
+
+// The numeric code of sppark_msm_tune_tail -> switches.  False: the code is refused (hipErrorInvalidValue).
+//
+//   code     switches                                  what runs instead
+//   0        none                                      --
+//   1        no_join, no_piece_tree                    the fan-in tree over every record (and make_plan's fan-in 4)
+//   2        no_narrow_end                             k_reduce_runs for every level
+//   3        no_latency_sums                           k_bucket_level1 / k_bucket_levelN; no small windows' sums
+//   4        no_coop                                   the one-wave-per-operation kernels
+//   5        no_piece_tree                             k_join_runs / the fan-in tree at the small sizes too
+//   6        convert_per_lane                          k_convert_points
+//   7        top_per_sum                               k_bucket_top_bits_coop with one work-group per sum
+//   8        piece_level_launches                      k_piece_level_coop for every level
+//   10       sums_one_lane                             k_bucket_level1_lat / k_bucket_levelN_lat
+//   16 + x   piece_fuse_max = 2^x  (x <= 63)           k_piece_tail_coop from the first level of <= 2^x work items
+//   9, 11 ... 15                                       nothing: as 0
+//   >= 80    refused: 2^x does not fit a size_t.  (The limit is compared with buckets x pair slots of a level, at most
+//            128 windows x 2^23 buckets x 2^9 pairs = 2^39: that product cannot overflow, and every x >= 39 means "all levels".)
+static inline bool decode_tail_code(unsigned code, msm_switches& s)
+{
+    s = msm_switches();
+    if (code >= 16 + 64) return false;
+    switch (code) {
+    case 1:  s.no_join = s.no_piece_tree = true; break;
+    case 2:  s.no_narrow_end = true; break;
+    case 3:  s.no_latency_sums = true; break;
+    case 4:  s.no_coop = true; break;
+    case 5:  s.no_piece_tree = true; break;
+    case 6:  s.convert_per_lane = true; break;
+    case 7:  s.top_per_sum = true; break;
+    case 8:  s.piece_level_launches = true; break;
+    case 10: s.sums_one_lane = true; break;
+    default: if (code >= 16) s.piece_fuse_max = (size_t)1 << (code - 16);
+    }
+    return true;
+}
 
 struct msm_plan {
     unsigned n, wbits, nwins, NB;       // wbits = longest window, NB = 2^(wbits-1) buckets per window
@@ -29,7 +82,7 @@ struct msm_tunables {                   // 0 = automatic
     unsigned records = 0;               // level-A sort records: 0 = 4 bytes unless a slab count is given, 1 = 8 bytes, 2 = 4 bytes also with a given slab count (rounded to power-of-two slabs)
     unsigned groups = 0;                // window groups (1 = everything on one stream)
     unsigned top = 0;                   // bucket sums: items per window handed to the subset-sum top (0 = 4096, 1 = never)
-    unsigned join = 0;                  // record list: 1 = no k_join_runs (every segment through the fan-in tree), 2 = no one-launch narrow end, 3 = no low-latency bucket-sum kernels, 4 = no cooperative (four waves per operation) kernels (A/B switches)
+    msm_switches sw;                    // A/B switches of the tail (decode_tail_code)
     unsigned K1 = 0;                    // bucket sums: buckets per work item of the first level (0 = K)
     unsigned g2_coop = 0;               // G2 only: the accumulation with one Fp2 component per wave (msm_g2c_kernels.hpp): 0 = for the 14-limb base fields, 1 = always, 2 = never
     unsigned long_runs = 0;             // set by the driver for G2 over the 14-limb base fields (the wave-pair accumulation): the run lengths of that kernel (make_plan)
@@ -156,7 +209,7 @@ static inline msm_plan make_plan(size_t npoints, unsigned scalar_bits, const msm
     // (round 4: 16 wherever k_join_runs runs first -- the driver's condition n / NB <= 4 L -- : the tree then sees only the
     // records of long segments, with uniform scalars none at all, and every level it does not have is an empty launch of
     // ~6 us saved: ten levels become four at 2^18 points)
-    const bool joined = t.join != 1 && (size_t)p.n / p.NB <= (size_t)4 * p.L;
+    const bool joined = !t.sw.no_join && (size_t)p.n / p.NB <= (size_t)4 * p.L;
     p.F = std::max(4u, t.F ? t.F : (joined ? 16u : 4u));
     p.K = t.K ? t.K : (lg <= 22 ? 4 : 8);
     p.K = std::min(p.K, p.NB);

@@ -97,8 +97,9 @@ class MsmContext:
         ffi.check(self.L, self.L.sppark_msm_tune_sums(self.h, top_items))
 
     def tune_tail(self, join=0, k1=0):
-        """join=1: no k_join_runs (every record segment through the fan-in tree); k1: buckets per work
-        item of the first bucket-sum level (0 = as the other levels)"""
+        """join: the numeric code of an A/B switch of the tail (0 = none, 1 = no k_join_runs, ...: the table at
+        decode_tail_code in csrc/msm/msm_plan.hpp; 80 and above are refused); k1: buckets per work item of the first
+        bucket-sum level (0 = as the other levels)"""
         ffi.check(self.L, self.L.sppark_msm_tune_tail(self.h, join, k1))
 
     def tune_pipeline(self, groups=0, chunk_points=0, max_scratch_bytes=0):

@@ -348,6 +348,7 @@ def test_msm_tail_variants(oracle, libs, curve, name):
                 ctx.tune(**plan); ctx.tune_tail(join, k1)
                 out = ctx.invoke(pts, scal)
                 assert (sppark_amd.to_affine(out, name) == exp).all(), (plan, join, k1)
+    assert pytest.raises(sppark_amd.SpparkError, ctx.tune_tail, 16 + 64, 0)     # 2^64 work items: no such limit
     ctx.close()
 
 

@@ -2,9 +2,12 @@
 // (ntt/ntt.cuh:31-366, ntt/parameters.cuh:222-337): order/direction/type
 // dispatch, per-(device, size, direction) twiddle tables built once on the
 // device and kept for the life of the process, kernel sequence on one stream.
+// WHAT runs is decided in ntt_route.hpp (make_ntt_route: a pure function); run() here fetches the tables a route asks
+// for and launches its steps.
 #pragma once
 #include "ntt_kernels.hpp"
 #include "ntt_r64_kernels.hpp"
+#include "ntt_route.hpp"
 #include "../ff/fr256_dev.hpp"
 #include "../ff/mont_host.hpp"
 #include "../util/runtime.hpp"
@@ -13,10 +16,6 @@
 #include <tuple>
 
 namespace sppark_amd {
-
-enum { NTT_NN = 0, NTT_NR = 1, NTT_RN = 2, NTT_RR = 3 };       // ntt/ntt.cuh:33
-enum { NTT_FORWARD = 0, NTT_INVERSE = 1 };                     // ntt/ntt.cuh:34
-enum { NTT_STANDARD = 0, NTT_COSET = 1 };                      // ntt/ntt.cuh:35
 
 // ---- host-side constants (parameter setup only; no transform code here) ------
 template<class F> struct host_field;
@@ -70,90 +69,54 @@ template<class P> struct host_field<fr256_dev<P>> {
 template<class F>
 class ntt_engine {
     struct table_set { F *lo, *hi, *inner, *glo, *ghi; unsigned h; F scale; };
-    // Inter-pass twiddle tables.  W = w_n^(n / n_cur) is the primitive n_cur-th root whatever the transform size n, so an
-    // unscaled table is shared by every size and keyed (device, direction, family, a, b, 0): family 0 = k_pass_table
-    // (a = lg_cur, b = S), family 1 = k_r64_table (a = kind, b = lg_cur).  A table that also carries 1/n belongs to one
-    // size: its key ends in lg n.  (Round 3 kept one copy per (size, direction): a forward + inverse 2^24 transform of a
-    // 256-bit field pinned > 1.1 GB, and more for every further size.)
+    // Inter-pass twiddle tables, keyed (device, direction) + the key of the route's table request (ntt_route.hpp
+    // ntt_table_req: shared by every transform size unless the table carries 1/n or coset powers).  (Round 3 kept one copy
+    // per (size, direction): a forward + inverse 2^24 transform of a 256-bit field pinned > 1.1 GB, and more for every
+    // further size.)
     typedef std::tuple<int, int, int, unsigned, unsigned, unsigned> tw_key;
     std::map<tw_key, F*> tw_cache;
-    // the radix-64 plan (ntt_r64_kernels.hpp): single-word fields, transforms of >= 2^12 elements
-    static constexpr bool R64 = sizeof(F) <= 8;
-    static constexpr unsigned R64_DIRECT_MAX_LG = 20;          // one inter-pass table up to 2^20 entries, two small ones above
-    static constexpr unsigned PASS_TABLE_MAX_LG = 16;          // tables of <= 2^16 elements (512 KB for Goldilocks): L2-resident
+    static constexpr bool R64 = sizeof(F) <= 8;                    // the radix-64 plan's kernels exist (ntt_r64_kernels.hpp)
     std::map<std::tuple<int, unsigned, int>, table_set> cache;     // (hip device, lg, inverse)
     std::mutex mtx;
+    template<unsigned N> using uint_c = std::integral_constant<unsigned, N>;
 
-    // columns per tile row (single-word fields: one 128-byte line; 256-bit fields: 16 elements =
-    // 512 bytes, so that a 4-stage tile still has 64 register sub-transforms) / elements per LDS tile
-    static constexpr unsigned LG_LINE = sizeof(F) == 4 ? 5 : sizeof(F) == 8 ? 4 : 4;
-    static constexpr unsigned LG_TILE = sizeof(F) == 4 ? 13 : sizeof(F) == 8 ? 12 : 10;
-    // stages per pass.  256-bit elements: radix-4 x radix-4 (S = 4).  Larger register radices keep
-    // 8 or 16 eight-word elements per lane (152 VGPRs, scratch) and measured slower in spite of
-    // fewer passes: 2^24 in 2.8 ms with S = 4, 3.3 ms with S = 6 (tools/gpu_ntt_wide_knobs.py).
-    // Round 3, with the twiddle tables and the <3, 3> kernel freed of its scratch use (its eight-element write-out loop
-    // is above clang's #pragma-unroll budget; -mllvm -pragma-unroll-threshold=200000: 193 VGPRs, no scratch): 2.55 ms
-    // with S = 6 against 2.54 with S = 4 on the same box, S = 5 2.81 -- a third fewer instructions and two passes less
-    // buy nothing at two waves per SIMD (LDS: 256 B per lane).  Not instantiated.  profiles/r03_ntt_wide_stages.log
-    static constexpr unsigned S_MAX = sizeof(F) > 8 ? 4 : 8;
-    // Round 4: the 256-bit fields run passes of up to 8 stages with ONE butterfly per lane and stage and the tile in LDS
-    // throughout (k_ntt_pass_lat, ntt_kernels.hpp): S/2 + 1 products per element for S stages instead of 3.75 for 4, half
-    // the passes -- and half the dependent chain on the small, latency-bound sizes.  0 = the register passes above.
-    static constexpr unsigned LAT_SMAX = sizeof(F) > 8 ? 8 : 0;
-
-    // 256-bit elements: tables up to 2^24 entries (512 MB; every sub-problem of the pass reads its table once, the small
-    // ones from L2 / the Infinity Cache).  The per-element alternative is a lo x hi product per twiddle: one of the ~3.5
-    // products per element and pass.  BLS12-381 Fr 2^24 forward (profiles/r03_ntt_wide_tables.log): 2.80 ms without
-    // tables, 2.43 with tables up to 2^16, 2.33 up to 2^20, 2.25 up to 2^24 -- even the table as large as the data pays,
-    // the passes are bound by their products.  (Tuning builds, -DSPPARK_TUNING: SPPARK_NTT_WIDE_TABLE=<log2> moves the
-    // limit, 0 = no tables.)
-    static unsigned wide_table_lg()
+    // The plan's shape parameters (ntt_route.hpp ntt_knobs).  A shipped library uses the defaults; a tuning build
+    // (-DSPPARK_TUNING, e.g. SPPARK_EXTRA_FLAGS=-DSPPARK_TUNING python -m sppark_amd.build; tools/gpu_ntt_sweep.py) reads
+    // them from the environment once per process.  The LDS tile is clamped to what the element size allows (160 KB per
+    // work-group: 2^14 eight-byte elements, 2^12 32-byte ones; the one-stage-per-round passes stay within the
+    // 64 KB a launch gets without raising the kernel's limit).
+    static const ntt_knobs& knobs()
     {
+        static const ntt_knobs knobs = [] {
+            const ntt_field f = ntt_field_of<F>();
+            ntt_knobs k = ntt_default_knobs(f);
 #ifdef SPPARK_TUNING
-        static const unsigned v = [] { const char* e = getenv("SPPARK_NTT_WIDE_TABLE"); return e ? (unsigned)atoi(e) : 24u; }();
-        return v;
-#else
-        return 24u;
+            const unsigned S_MAX = k.smax;
+            // 256-bit fields: stages per one-stage-per-round pass (0: the register passes), columns per tile row and tile
+            // elements (log2; default: by size, make_ntt_lat_plan)
+            if (const char* e = getenv("SPPARK_NTT_LAT_SMAX")) { unsigned v = (unsigned)atoi(e); if (v <= 8) k.lat_smax = R64 ? 0 : v; }
+            if (const char* e = getenv("SPPARK_NTT_LAT_LGC")) { int v = atoi(e); if (v >= 0 && v <= 3) k.lat_lgc = v; }
+            if (const char* e = getenv("SPPARK_NTT_LAT_LGTILE")) { int v = atoi(e); if (v >= 6 && v <= 11) k.lat_lgt = v; }
+            if (const char* e = getenv("SPPARK_NTT_COSET_FOLD")) k.coset_fold = (unsigned)atoi(e);    // 0: the separate scaling launch
+            if (const char* e = getenv("SPPARK_NTT_R64_MIN")) k.r64_min = (unsigned)atoi(e);          // 99: the 8-stage plan only
+            if (const char* e = getenv("SPPARK_NTT_R64_DIRECT")) k.r64_direct = (unsigned)atoi(e);    // largest single inter-pass table (log2)
+            if (const char* e = getenv("SPPARK_NTT_SMAX")) { unsigned v = (unsigned)atoi(e); if (v >= 1 && v <= S_MAX) k.smax = v; }
+            if (const char* e = getenv("SPPARK_NTT_LGC")) { unsigned v = (unsigned)atoi(e); if (v >= 1 && v <= 8) k.lgc = v; }
+            if (const char* e = getenv("SPPARK_NTT_LGTILE")) {
+                unsigned v = (unsigned)atoi(e), cap = 17;
+                while (((size_t)sizeof(F) << cap) > 160 * 1024) cap--;
+                if (v >= 8 && v <= cap) k.lgt = v;
+            }
+            if (const char* e = getenv("SPPARK_NTT_WIDE_TABLE")) k.wide_table_lg = (unsigned)atoi(e);                    // 0 = no tables
+            if (const char* e = getenv("SPPARK_NTT_SMALL_MAX")) k.small_max = std::min((unsigned)atoi(e), f.small_cap);    // 0 = never
+            if (const char* e = getenv("SPPARK_NTT_PACKED_MAX")) k.packed_max = std::min((unsigned)atoi(e), NTT_PACKED_MAX_LG);   // 0 = never
+            if (const char* e = getenv("SPPARK_NTT_SMALL_SIZED")) k.small_sized = atoi(e) != 0;    // 0: the run-time-size instance at every size
 #endif
+            if (k.lgt < k.smax + 1) k.lgt = k.smax + 1;
+            return k;
+        }();
+        return knobs;
     }
-    // transforms up to this size run as one launch of one work-group: 2^11 for the single-word fields, 2^9 for the 256-bit
-    // ones (at 2^10 their two one-stage-per-round launches are as fast as eight waves of 256-bit exchanges through
-    // LDS: 17.7 against 17.8 us, profiles/r05_ntt_small_sized_ab.log).  Tuning builds: SPPARK_NTT_SMALL_MAX, 0 = never.
-    static unsigned small_max_lg()
-    {
-        static constexpr unsigned cap = ntt_small_cap<F>::value, dflt = sizeof(F) > 8 ? cap - 1 : cap;
-#ifdef SPPARK_TUNING
-        static const unsigned v = [] { const char* e = getenv("SPPARK_NTT_SMALL_MAX"); return e ? std::min((unsigned)atoi(e), cap) : dflt; }();
-        return v;
-#else
-        return dflt;
-#endif
-    }
-    // batched transforms of up to this size run several columns per wave (k_ntt_small_packed, at most NTT_PACKED_MAX_LG = 6);
-    // above it one work-group per column.  Tuning builds: SPPARK_NTT_PACKED_MAX, 0 = never (DESIGN.md "Batched transforms")
-    static unsigned packed_max_lg()
-    {
-#ifdef SPPARK_TUNING
-        static const unsigned v = [] { const char* e = getenv("SPPARK_NTT_PACKED_MAX"); return e ? std::min((unsigned)atoi(e), NTT_PACKED_MAX_LG) : NTT_PACKED_MAX_LG; }();
-        return v;
-#else
-        return NTT_PACKED_MAX_LG;
-#endif
-    }
-    // tuning builds: SPPARK_NTT_SMALL_SIZED=0 runs every size through the run-time-size instance
-    static bool small_sized()
-    {
-#ifdef SPPARK_TUNING
-        static const bool v = [] { const char* e = getenv("SPPARK_NTT_SMALL_SIZED"); return !e || atoi(e) != 0; }();
-        return v;
-#else
-        return true;
-#endif
-    }
-    // the inter-pass twiddle table of a pass on sub-problems of 2^lg_cur elements (built once per
-    // (device, size, direction, pass shape); null when the pass generates its twiddles instead)
-    static bool has_pass_table(unsigned lg_cur, unsigned S)
-    {   return !(lg_cur > (ntt_gen_twiddles<F>::value ? PASS_TABLE_MAX_LG : wide_table_lg()) || lg_cur <= S || S / 2 == 0);   }
     // Find or build one table.  The engine lock is NOT held while the table is allocated, generated and synchronised
     // (another thread's transform of a cached size goes on meanwhile); two threads that miss the same key both build
     // it and the loser frees its copy.  Returns nullptr when the device has no room for it -- the idle scratch buffers
@@ -179,34 +142,35 @@ class ntt_engine {
         if (!ins.second) (void)hipFree(tw);                         // built twice: keep the first
         return ins.first->second;
     }
-    const F* pass_table(int hip_dev, unsigned lg, int inverse, unsigned lg_cur, unsigned S, int scaled, const ntt_tables<F>& T, hipStream_t stream)
+
+    // one table of a route (ntt_route.hpp ntt_table_req), found in the cache or built by its kernel; G: the powers of the
+    // coset generator
+    const F* route_table(int hip_dev, int inverse, const ntt_table_req& q, const ntt_tables<F>& T, const ntt_tables<F>& G, hipStream_t stream)
     {
-        if (!has_pass_table(lg_cur, S)) return nullptr;
-        const size_t n = (size_t)1 << lg_cur;
-        return cached_table(tw_key(hip_dev, inverse, 0, lg_cur, S, scaled ? lg : 0u), n, stream, [&](F* tw) {
-            hipLaunchKernelGGL(k_pass_table<F>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, tw, T, lg_cur, S, scaled);
+        const unsigned grid = (unsigned)((q.count + 255) / 256);
+        return cached_table(tw_key(hip_dev, inverse, q.key_family, q.key_a, q.key_b, q.key_c), q.count, stream, [&](F* t) {
+            switch (q.family) {
+                case NT_PASS: hipLaunchKernelGGL(k_pass_table<F>, dim3(grid), dim3(256), 0, stream, t, T, q.lg_cur, q.S, (int)q.scaled); break;
+                case NT_R64:  hipLaunchKernelGGL(k_r64_table<F>, dim3(grid), dim3(256), 0, stream, t, T, q.kind, q.lg_cur, (int)q.scaled, q.cmode, G); break;
+                case NT_CZ:   hipLaunchKernelGGL(k_r64_cz<F>, dim3(1), dim3(64), 0, stream, t, G, q.cmode); break;
+                case NT_CROW: hipLaunchKernelGGL(k_pass_crow<F>, dim3(1), dim3(256), 0, stream, t, G, q.cmode, q.S); break;
+            }
         });
     }
 
-    // a table of the radix-64 plan (r64_table_item); |cmode|: with the coset powers folded in (G: the powers of g), which
-    // ties it to the transform size
-    const F* r64_table(int hip_dev, unsigned lg, int inverse, unsigned kind, unsigned lg_cur, int scaled,
-                       const ntt_tables<F>& T, hipStream_t stream, unsigned cmode, const ntt_tables<F>& G)
+    // (gs, inverse) -> the DIF and INV template arguments of the transform kernels, as compile-time constants
+    template<class Fn> static void with_dif_inv(bool gs, bool inverse, Fn&& fn)
     {
-        if (cmode == 2 && kind == 2) cmode = 0;                     // (no row-only part: the plain table)
-        const size_t count = kind == 0 ? (size_t)1 << lg_cur : kind == 1 ? (size_t)1 << (lg_cur - 6) : 4096;
-        const tw_key key = cmode ? tw_key(hip_dev, inverse, 1 + 10 * (int)cmode, kind, lg_cur, lg | (scaled ? 256u : 0u))
-                                 : tw_key(hip_dev, inverse, 1, kind, lg_cur, scaled ? lg : 0u);
-        return cached_table(key, count, stream, [&](F* tw) {
-            hipLaunchKernelGGL(k_r64_table<F>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, tw, T, kind, lg_cur, scaled, cmode, G);
-        });
+        if (gs) { if (inverse) fn(std::true_type(), std::true_type()); else fn(std::true_type(), std::false_type()); }
+        else    { if (inverse) fn(std::false_type(), std::true_type()); else fn(std::false_type(), std::false_type()); }
     }
-    // the 64 constants of a folded coset transform (r64_cz_item)
-    const F* r64_cz(int hip_dev, unsigned lg, int inverse, unsigned cmode, const ntt_tables<F>& G, hipStream_t stream)
+    static void launch_bitrev(const ntt_step& s, F* d, unsigned lg, size_t col_stride, hipStream_t stream)
     {
-        return cached_table(tw_key(hip_dev, inverse, 2, cmode, 0u, lg), 64, stream, [&](F* cz) {
-            hipLaunchKernelGGL(k_r64_cz<F>, dim3(1), dim3(64), 0, stream, cz, G, cmode);
-        });
+        constexpr unsigned TB = bitrev_tile_bits<F>::value;
+        const dim3 grid(s.gx, s.gy), block(s.block);
+        if (s.kernel == NK_BITREV) hipLaunchKernelGGL(k_bitrev<F>, grid, block, 0, stream, d, lg, col_stride);
+        else if (s.kernel == NK_BITREV_TILED) hipLaunchKernelGGL((k_bitrev_tiled<F, TB>), grid, block, s.lds, stream, d, lg, col_stride);
+        else if constexpr (sizeof(F) <= 8) hipLaunchKernelGGL((k_bitrev_tiled_vec<F, TB>), grid, block, s.lds, stream, d, lg, col_stride);
     }
 
     table_set tables(int hip_dev, unsigned lg, int inverse, hipStream_t stream)
@@ -255,282 +219,152 @@ public:
     // in-place transform of a DEVICE buffer of 2^lg elements on |stream|
     // |lde| (sppark_lde's forward RN transform only): the input is still the COMPACT coefficients lde->src (2^lg_domain, bit-reversed
     // order, unshifted); the first step of the radix-64 plan reads them as the spread array (k_ntt12<.., LDE>), and where the
-    // transform runs another plan the spread is launched here first.
+    // transform runs another plan the spread is a step of its own in front.
     // |lde->out| instead (sppark_lde's inverse NR transform): the result goes to |out|, |d| is scratch afterwards -- the last step
     // of the radix-64 plan stores there (ntt_r64_args::out), any other plan runs in place and copies.
-    // |batch| columns (sppark_ntt_batch / sppark_lde_batch): column j at d + j * col_stride.  Every launch below takes one grid
+    // |batch| columns (sppark_ntt_batch / sppark_lde_batch): column j at d + j * col_stride.  Every launch takes one grid
     // row per column (blockIdx.y; the packed kernel: one per work-group of columns) and the columns share the tables; lde->src
     // and lde->out then hold the columns packed, 2^lde->lg_domain and 2^lg elements apart.  A batch above what one launch can
-    // index (launch_cols) runs as several launch chunks.
+    // index (launch_cols) runs as several launch chunks, each with a route of its own.
     struct lde_input { const F* src; unsigned lg_domain, lg_blowup; F* out; };
     void run(const gpu_info& gpu, F* d, unsigned lg, int order, int direction, int type, hipStream_t stream, const lde_input* lde = nullptr,
              size_t batch = 1, size_t col_stride = 0)
     {
-        if (batch > 1) {
-            const size_t per = launch_cols(gpu, lg);
-            if (batch > per) {
-                for (size_t c0 = 0; c0 < batch; c0 += per) {
-                    lde_input sub{};
-                    if (lde) { sub = *lde; if (sub.src) sub.src += c0 << lde->lg_domain; if (sub.out) sub.out += c0 << lg; }
-                    run(gpu, d + c0 * col_stride, lg, order, direction, type, stream, lde ? &sub : nullptr, std::min(per, batch - c0), col_stride);
-                }
-                return;
-            }
+        ntt_call call;
+        call.lg = lg; call.order = order; call.direction = direction; call.type = type;
+        call.col_stride = col_stride; call.max_grid_y = (size_t)std::max(gpu.prop.maxGridSize[1], 1);
+        if (lde) { call.lde = lde->out ? NL_OUT : NL_SPREAD; call.lg_domain = lde->lg_domain; call.lg_blowup = lde->lg_blowup; }
+        const size_t per = launch_cols(gpu, lg);
+        for (size_t c0 = 0; c0 < batch; c0 += per) {
+            call.batch = std::min(per, batch - c0);
+            F* dc = d + c0 * col_stride;
+            call.aligned16 = ((uintptr_t)dc & 15) == 0 && (call.batch == 1 || ((col_stride * sizeof(F)) & 15) == 0);
+            lde_input sub{};
+            if (lde) { sub = *lde; if (sub.src) sub.src += c0 << lde->lg_domain; if (sub.out) sub.out += c0 << lg; }
+            run_chunk(gpu, dc, call, sub, stream);
         }
-        if (lg == 0) {                                              // ntt/ntt.cuh:220-221 (one element: the hand-over of sppark_lde still happens)
-            if (lde && lde->out) copy_cols(lde->out, 1, d, col_stride, 1, batch, stream);
-            else if (lde) lde_spread(gpu, d, lde->src, lde->lg_domain, lde->lg_blowup, true, stream, batch, col_stride, 1);
-            return;
-        }
-        if (lg > F::TWO_ADICITY || order < 0 || order > 3) HIP_OK(hipErrorInvalidValue);
-        const int inverse = direction == NTT_INVERSE;
-        const table_set ts = tables(gpu.hip_id, lg, inverse, stream);
-        ntt_tables<F> T{ts.lo, ts.hi, ts.inner, lg, ts.h, ts.scale, nullptr}, G{ts.glo, ts.ghi, nullptr, lg, ts.h, ts.scale, nullptr};
-        const size_t n = (size_t)1 << lg;
-        const unsigned egrid = (unsigned)std::min<size_t>((n + 255) / 256, (size_t)1 << 22);   // (k_coset strides past 2^30)
-
-        // up to 2^11 elements (256-bit fields: 2^9): the whole transform -- permutations, coset powers and 1/n included -- by one work-group
-        // in one launch (k_ntt_small, ntt_kernels.hpp)
-        F* final_out = lde ? lde->out : nullptr;
-        if (final_out) lde = nullptr;
-        if (lde && lg <= small_max_lg()) {
-            lde_spread(gpu, d, lde->src, lde->lg_domain, lde->lg_blowup, true, stream, batch, col_stride, (size_t)1 << lde->lg_domain);
-            lde = nullptr;
-        }
-        if (lg <= small_max_lg() && batch > 1 && lg <= packed_max_lg()) {         // several columns per wave (k_ntt_small_packed)
-            const unsigned flags = ntt_small_flags(order, inverse != 0, type == NTT_COSET);
-            const unsigned groups = (unsigned)((batch + (256u >> (lg - 1)) - 1) >> (9 - lg));
-#define SPPARK_NTT_PACKED_PICK(LG) do { \
-                if (inverse) hipLaunchKernelGGL((k_ntt_small_packed<F, true, LG>), dim3(1, groups), dim3(256), 0, stream, d, T, G, flags, col_stride, batch); \
-                else         hipLaunchKernelGGL((k_ntt_small_packed<F, false, LG>), dim3(1, groups), dim3(256), 0, stream, d, T, G, flags, col_stride, batch); } while (0)
-            switch (lg) {
-                case 1: SPPARK_NTT_PACKED_PICK(1); break;
-                case 2: SPPARK_NTT_PACKED_PICK(2); break;
-                case 3: SPPARK_NTT_PACKED_PICK(3); break;
-                case 4: SPPARK_NTT_PACKED_PICK(4); break;
-                case 5: SPPARK_NTT_PACKED_PICK(5); break;
-                default: SPPARK_NTT_PACKED_PICK(6); break;
-            }
-#undef SPPARK_NTT_PACKED_PICK
-            HIP_OK(hipGetLastError());
-            if (final_out) copy_cols(final_out, n, d, col_stride, n, batch, stream);
-            return;
-        }
-        if (lg <= small_max_lg()) {
-            const unsigned flags = ntt_small_flags(order, inverse != 0, type == NTT_COSET);
-            const unsigned lanes = (unsigned)std::max<size_t>(64, n / 2);
-            const size_t lds = lanes > 64 ? 2 * (size_t)lanes * sizeof(F) : 0;        // the exchanges across waves (ntt_rx_regroup)
-            // (single-word fields: the sizes 2^8 ... 2^11 have their own instance, compiled for that size)
-#define SPPARK_NTT_SMALL_PICK(LGC) do { \
-                if (inverse) hipLaunchKernelGGL((k_ntt_small<F, true, LGC>), dim3(1, (unsigned)batch), dim3(lanes), lds, stream, d, T, G, flags, col_stride); \
-                else         hipLaunchKernelGGL((k_ntt_small<F, false, LGC>), dim3(1, (unsigned)batch), dim3(lanes), lds, stream, d, T, G, flags, col_stride); } while (0)
-            if constexpr (sizeof(F) <= 8) {
-                switch (small_sized() ? lg : 0u) {
-                    case 8:  SPPARK_NTT_SMALL_PICK(8); break;
-                    case 9:  SPPARK_NTT_SMALL_PICK(9); break;
-                    case 10: SPPARK_NTT_SMALL_PICK(10); break;
-                    case 11: SPPARK_NTT_SMALL_PICK(11); break;
-                    default: SPPARK_NTT_SMALL_PICK(0); break;
-                }
-            } else
-                SPPARK_NTT_SMALL_PICK(0);
-#undef SPPARK_NTT_SMALL_PICK
-            HIP_OK(hipGetLastError());
-            if (final_out) copy_cols(final_out, n, d, col_stride, n, batch, stream);
-            return;
-        }
-
-        bool bitrev, gs;
-        switch (order) {
-            case NTT_NN: bit_reverse(d, lg, stream, batch, col_stride);
-                         bitrev = true;  gs = false; break;
-            case NTT_NR: bitrev = false; gs = true;  break;
-            case NTT_RN: bitrev = true;  gs = false; break;
-            default:     bitrev = true;  gs = true;  break;
-        }
-        // The plan's shape parameters.  A shipped library uses the constants; a tuning build (-DSPPARK_TUNING, e.g.
-        // SPPARK_EXTRA_FLAGS=-DSPPARK_TUNING python -m sppark_amd.build; tools/gpu_ntt_sweep.py) reads them from the
-        // environment once per process.  The LDS tile is clamped to what the element size allows (160 KB per
-        // work-group: 2^14 eight-byte elements, 2^12 32-byte ones; the one-stage-per-round passes stay within the
-        // 64 KB a launch gets without raising the kernel's limit).
-        struct knobs_t { unsigned smax, lgc, lgt, r64_min, r64_direct, lat_smax; int lat_lgc, lat_lgt; unsigned coset_fold; };
-        static const knobs_t knobs = [] {
-            knobs_t k{S_MAX, LG_LINE, LG_TILE, 12, R64_DIRECT_MAX_LG, LAT_SMAX, -1, -1, 1};
-#ifdef SPPARK_TUNING
-            // 256-bit fields: stages per one-stage-per-round pass (0: the register passes), columns per tile row and tile
-            // elements (log2; default: by size, lat_shape())
-            if (const char* e = getenv("SPPARK_NTT_LAT_SMAX")) { unsigned v = (unsigned)atoi(e); if (v <= 8) k.lat_smax = R64 ? 0 : v; }
-            if (const char* e = getenv("SPPARK_NTT_LAT_LGC")) { int v = atoi(e); if (v >= 0 && v <= 3) k.lat_lgc = v; }
-            if (const char* e = getenv("SPPARK_NTT_LAT_LGTILE")) { int v = atoi(e); if (v >= 6 && v <= 11) k.lat_lgt = v; }
-            if (const char* e = getenv("SPPARK_NTT_COSET_FOLD")) k.coset_fold = (unsigned)atoi(e);    // 0: the separate scaling launch
-            if (const char* e = getenv("SPPARK_NTT_R64_MIN")) k.r64_min = (unsigned)atoi(e);          // 99: the 8-stage plan only
-            if (const char* e = getenv("SPPARK_NTT_R64_DIRECT")) k.r64_direct = (unsigned)atoi(e);    // largest single inter-pass table (log2)
-            if (const char* e = getenv("SPPARK_NTT_SMAX")) { unsigned v = (unsigned)atoi(e); if (v >= 1 && v <= S_MAX) k.smax = v; }
-            if (const char* e = getenv("SPPARK_NTT_LGC")) { unsigned v = (unsigned)atoi(e); if (v >= 1 && v <= 8) k.lgc = v; }
-            if (const char* e = getenv("SPPARK_NTT_LGTILE")) {
-                unsigned v = (unsigned)atoi(e), cap = 17;
-                while (((size_t)sizeof(F) << cap) > 160 * 1024) cap--;
-                if (v >= 8 && v <= cap) k.lgt = v;
-            }
-#endif
-            if (k.lgt < k.smax + 1) k.lgt = k.smax + 1;
-            return k;
-        }();
-        const unsigned smax = knobs.smax, lgc = knobs.lgc, lgt = knobs.lgt;
-        ntt_plan pl;
-        r64_plan rp; rp.nsteps = 0;
-        // the tables of the radix-64 plan, fetched (first call: built) BEFORE anything is launched: if the device has no
-        // room for one of them the transform runs the 8-stage plan, whose passes can generate their twiddles
-        const F* r64_tabs[8][2] = {};
-        // a coset transform on a plan of k_ntt6 / k_ntt12 steps carries the powers of the coset generator in its tables and 64
-        // constants (r64_coset_mode, ntt_r64_kernels.hpp): no separate scaling launch (2^24: 0.217 -> 0.19 ms)
-        unsigned cmode = 0;
-        const F* r64_czp = nullptr;
-        const F* top_crow = nullptr;
-        if (R64 && lg >= 12 && lg >= knobs.r64_min) {
-            rp = make_r64_plan(lg);
-            cmode = knobs.coset_fold ? r64_coset_mode(rp, gs, inverse != 0, type == NTT_COSET && order != NTT_RR) : 0;
-            bool ok = true;
-            for (unsigned i = 0; i < rp.nsteps && ok; i++) {
-                const r64_step st = rp.step[gs ? i : rp.nsteps - 1 - i];
-                if (st.kind == 0) continue;
-                const int scaled = inverse && i == rp.nsteps - 1;
-                const unsigned cm = cmode == 1 && st.lg_cur != lg ? 0 : cmode;     // natural exponents: the step on the whole transform only
-                if (st.kind == 2 || st.lg_cur <= knobs.r64_direct)
-                    ok = (r64_tabs[i][0] = r64_table(gpu.hip_id, lg, inverse, 0, st.lg_cur, scaled, T, stream, cm, G)) != nullptr;
-                else
-                    ok = (r64_tabs[i][0] = r64_table(gpu.hip_id, lg, inverse, 1, st.lg_cur, scaled, T, stream, cm, G)) != nullptr
-                      && (r64_tabs[i][1] = r64_table(gpu.hip_id, lg, inverse, 2, st.lg_cur, 0, T, stream, cm, G)) != nullptr;
-            }
-            if (ok && cmode) ok = (r64_czp = r64_cz(gpu.hip_id, lg, inverse, cmode, G, stream)) != nullptr;
-            // (a generic pass on top of the plan takes its share as 2^S row constants: g^(row << lgQ) / g^(rev_S(row)))
-            if (ok && cmode && rp.step[0].kind == 0) {
-                const unsigned S = rp.step[0].S;
-                ok = (top_crow = cached_table(tw_key(gpu.hip_id, inverse, 3, cmode, S, lg), (size_t)1 << S, stream, [&](F* t) {
-                          hipLaunchKernelGGL(k_pass_crow<F>, dim3(1), dim3(256), 0, stream, t, G, cmode, S);
-                      })) != nullptr;
-            }
-            if (!ok) { rp.nsteps = 0; cmode = 0; top_crow = nullptr; }
-        }
-        // sppark_lde: the spread + coset shift inside the first step where that is k_ntt12 on a forward RN transform with at
-        // most 8 positions per coefficient; otherwise as a launch of its own, now
-        bool lde_fused = false;
-        if (lde) {
-            if constexpr (R64)
-                lde_fused = rp.nsteps && !gs && !inverse && order == NTT_RN && type == NTT_STANDARD && rp.step[rp.nsteps - 1].kind == 2
-                         && lde->lg_blowup >= 1 && lde->lg_blowup <= 3 && lde->lg_domain + lde->lg_blowup == lg;
-            if (!lde_fused) lde_spread(gpu, d, lde->src, lde->lg_domain, lde->lg_blowup, true, stream, batch, col_stride, (size_t)1 << lde->lg_domain);
-        }
-        const unsigned ncol = (unsigned)batch;                     // (<= launch_cols: the grid's y dimension)
-        if (!inverse && type == NTT_COSET && !cmode)
-            hipLaunchKernelGGL(k_coset<F>, dim3(egrid, ncol), dim3(256), 0, stream, d, G, (int)bitrev, col_stride);
-        const bool lat = !R64 && knobs.lat_smax != 0;
-        if (rp.nsteps) pl.npass = rp.nsteps;
-        else if (lat)  pl = make_ntt_lat_plan(lg, knobs.lat_smax, knobs.lat_lgc, knobs.lat_lgt);
-        else           pl = make_ntt_plan(lg, lgc, lgt, smax);
-        int scale_pass = -1;                        // (the radix-64 plan folds the scaling into its own last table)
-        if (inverse && !rp.nsteps) {
-            unsigned best = ~0u;
-            for (unsigned i = 0; i < pl.npass; i++) {
-                const ntt_pass& q = pl.pass[gs ? i : pl.npass - 1 - i];
-                if (has_pass_table(q.lg_cur, q.S) && q.lg_cur < best) { best = q.lg_cur; scale_pass = (int)i; }
-            }
-        }
-        for (unsigned i = 0; i < pl.npass; i++) {
-            const bool last = i == pl.npass - 1;
-            ntt_pass P;
-            P.cmode = 0; P.crow = P.cg_lo = P.cg_hi = nullptr; P.cg_h = 0;
-            if (rp.nsteps) {
-                const r64_step st = rp.step[gs ? i : rp.nsteps - 1 - i];
-                if constexpr (R64) {
-                    if (st.kind != 0) {
-                        ntt_r64_args<F> A{T.inner, nullptr, nullptr, nullptr, st.lg_cur, nullptr};
-                        if (cmode == 2 ? st.kind == 2 : (cmode == 1 && st.lg_cur == lg)) A.cz = r64_czp;
-                        if (st.kind == 2 || st.lg_cur <= knobs.r64_direct) A.tw = r64_tabs[i][0];
-                        else { A.t1 = r64_tabs[i][0]; A.t2 = r64_tabs[i][1]; }
-                        const unsigned tiles = (unsigned)(n >> 12);
-                        const size_t lds = sizeof(F) << 12;
-#define SPPARK_R64_LAUNCH(K)                                                                                   \
-                        do {                                                                                   \
-                            if (gs) { if (inverse) hipLaunchKernelGGL((K<F, true, true>), dim3(tiles, ncol), dim3(512), lds, stream, d, A, col_stride);    \
-                                      else         hipLaunchKernelGGL((K<F, true, false>), dim3(tiles, ncol), dim3(512), lds, stream, d, A, col_stride); } \
-                            else    { if (inverse) hipLaunchKernelGGL((K<F, false, true>), dim3(tiles, ncol), dim3(512), lds, stream, d, A, col_stride);   \
-                                      else         hipLaunchKernelGGL((K<F, false, false>), dim3(tiles, ncol), dim3(512), lds, stream, d, A, col_stride); } \
-                        } while (0)
-                        if (final_out && last && st.kind == 2 && gs) { A.out = final_out; A.aux_stride = n; final_out = nullptr; }
-                        if (lde_fused && i == 0) {
-                            const table_set tg = tables(gpu.hip_id, lde->lg_domain, 0, stream);
-                            A.lde_src = lde->src; A.lde_glo = tg.glo; A.lde_ghi = tg.ghi; A.lde_gh = tg.h;
-                            A.lde_lgd = lde->lg_domain; A.lde_lgb = lde->lg_blowup; A.aux_stride = (size_t)1 << lde->lg_domain;
-                            hipLaunchKernelGGL((k_ntt12<F, false, false, true>), dim3(tiles, ncol), dim3(512), lds, stream, d, A, col_stride);
-                        } else if (st.kind == 1) SPPARK_R64_LAUNCH(k_ntt6); else SPPARK_R64_LAUNCH(k_ntt12);
-#undef SPPARK_R64_LAUNCH
-                        continue;
-                    }
-                }
-                P.lg_cur = st.lg_cur; P.S = st.S; P.lgC = lgc; P.lgG = 0;       // a strided pass above >= 12 further stages
-                P.cmode = cmode; P.crow = top_crow; P.cg_lo = G.lo; P.cg_hi = G.hi; P.cg_h = G.h;      // (a folded coset transform)
-            } else {
-                P = pl.pass[gs ? i : pl.npass - 1 - i];
-            }
-            // 1/n of an inverse transform: carried by the table of the tabled pass on the smallest sub-problems when the
-            // plan has one (a product per element saved), applied by the last pass otherwise
-            const bool scale_here = inverse && scale_pass == (int)i;
-            T.pass_tw = pass_table(gpu.hip_id, lg, inverse, P.lg_cur, P.S, scale_here ? 1 : 0, T, stream);
-            if (scale_here && T.pass_tw == nullptr) {           // no room for the scaled table: the shared unscaled one (or
-                scale_pass = -1;                                // none), and the last pass multiplies by 1/n itself
-                T.pass_tw = pass_table(gpu.hip_id, lg, inverse, P.lg_cur, P.S, 0, T, stream);
-            }
-            P.apply_scale = inverse && last && scale_pass < 0;
-            size_t tile_elems = (size_t)1 << (P.lgG + P.S + P.lgC);
-            unsigned tiles = (unsigned)(n / tile_elems);
-            if constexpr (!R64) {
-                if (lat) {                                      // one butterfly per lane and stage, the tile in LDS throughout
-                    const unsigned lanes = (unsigned)std::min<size_t>(std::max<size_t>(tile_elems / 2, 64), 1024);
-                    const size_t lat_lds = tile_elems * sizeof(F);
-                    if (lat_lds > 64 * 1024) HIP_OK(hipErrorInvalidValue);      // (only a tuning build can ask for such a tile)
-                    if (gs) { if (inverse) hipLaunchKernelGGL((k_ntt_pass_lat<F, true, true>), dim3(tiles, ncol), dim3(lanes), lat_lds, stream, d, T, P, col_stride);
-                              else         hipLaunchKernelGGL((k_ntt_pass_lat<F, true, false>), dim3(tiles, ncol), dim3(lanes), lat_lds, stream, d, T, P, col_stride); }
-                    else    { if (inverse) hipLaunchKernelGGL((k_ntt_pass_lat<F, false, true>), dim3(tiles, ncol), dim3(lanes), lat_lds, stream, d, T, P, col_stride);
-                              else         hipLaunchKernelGGL((k_ntt_pass_lat<F, false, false>), dim3(tiles, ncol), dim3(lanes), lat_lds, stream, d, T, P, col_stride); }
-                    continue;
-                }
-            }
-            size_t lds = ntt_lds_elems(P) * sizeof(F);
-            // one lane per register sub-transform: a tile has 2^(lgG + R1 + lgC) of them in its
-            // larger round (small tiles of wide elements would leave most of 256 lanes idle)
-            const unsigned groups = 1u << (P.lgG + (P.S + 1) / 2 + P.lgC);
-            const unsigned nthr = groups >= 512 ? 512 : groups <= 64 ? 64 : groups;
-#define SPPARK_NTT_LAUNCH(R1, R2)                                                                              \
-            do {                                                                                               \
-                if (lds > 65536) {                                                                             \
-                    const void* fn = gs ? (inverse ? (const void*)k_ntt_pass<F, true, true, R1, R2> : (const void*)k_ntt_pass<F, true, false, R1, R2>)   \
-                                        : (inverse ? (const void*)k_ntt_pass<F, false, true, R1, R2> : (const void*)k_ntt_pass<F, false, false, R1, R2>); \
-                    HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));     \
-                }                                                                                              \
-                if (gs) { if (inverse) hipLaunchKernelGGL((k_ntt_pass<F, true, true, R1, R2>), dim3(tiles, ncol), dim3(nthr), lds, stream, d, T, P, col_stride);   \
-                          else         hipLaunchKernelGGL((k_ntt_pass<F, true, false, R1, R2>), dim3(tiles, ncol), dim3(nthr), lds, stream, d, T, P, col_stride); } \
-                else    { if (inverse) hipLaunchKernelGGL((k_ntt_pass<F, false, true, R1, R2>), dim3(tiles, ncol), dim3(nthr), lds, stream, d, T, P, col_stride);  \
-                          else         hipLaunchKernelGGL((k_ntt_pass<F, false, false, R1, R2>), dim3(tiles, ncol), dim3(nthr), lds, stream, d, T, P, col_stride); } \
-            } while (0)
-            if constexpr (S_MAX >= 8) { SPPARK_NTT_DISPATCH_S(P.S, SPPARK_NTT_LAUNCH); }
-            else                      { SPPARK_NTT_DISPATCH_S4(P.S, SPPARK_NTT_LAUNCH); }
-#undef SPPARK_NTT_LAUNCH
-        }
-        if (inverse && type == NTT_COSET && !cmode)
-            hipLaunchKernelGGL(k_coset<F>, dim3(egrid, ncol), dim3(256), 0, stream, d, G, (int)!bitrev, col_stride);
-        if (order == NTT_RR)
-            bit_reverse(d, lg, stream, batch, col_stride);
-        HIP_OK(hipGetLastError());
-        if (final_out) copy_cols(final_out, n, d, col_stride, n, batch, stream);      // (no step stored there)
     }
 
-    // columns one launch of run() covers: the grid's y dimension, times the columns of a work-group of k_ntt_small_packed
-    size_t launch_cols(const gpu_info& gpu, unsigned lg)
+private:
+    // one launch chunk: route, tables, launches
+    void run_chunk(const gpu_info& gpu, F* d, ntt_call call, const lde_input& lde, hipStream_t stream)
     {
-        const size_t rows = (size_t)std::max(gpu.prop.maxGridSize[1], 1);
-        return lg >= 1 && lg <= packed_max_lg() && lg <= small_max_lg() ? rows << (9 - lg) : rows;
+        const ntt_field fld = ntt_field_of<F>();
+        const unsigned lg = call.lg;
+        const size_t n = (size_t)1 << lg, col_stride = call.col_stride;
+        ntt_route r = make_ntt_route(fld, knobs(), call);
+        if (r.invalid || r.overflow) HIP_OK(hipErrorInvalidValue);
+        ntt_tables<F> T{}, G{};
+        const F* tab[ntt_route::TCAP] = {};
+        if (lg) {
+            const table_set ts = tables(gpu.hip_id, lg, r.inverse, stream);
+            T = ntt_tables<F>{ts.lo, ts.hi, ts.inner, lg, ts.h, ts.scale, nullptr}; G = ntt_tables<F>{ts.glo, ts.ghi, nullptr, lg, ts.h, ts.scale, nullptr};
+            // The tables, fetched (first call: built) BEFORE anything is launched.  If the device has no room for one of
+            // the radix-64 plan's, the transform runs the 8-stage plan, whose passes can generate their twiddles; if it has
+            // none for the table that carries 1/n, the shared unscaled one (or none) and the last pass multiplies by 1/n
+            // itself; without an unscaled inter-pass table a pass generates its twiddles.
+            for (unsigned i = 0; i < r.ntables; i++) {
+                const ntt_table_req& q = r.tables[i];
+                if ((tab[i] = route_table(gpu.hip_id, r.inverse, q, T, G, stream)) != nullptr || (q.family == NT_PASS && !q.scaled)) continue;
+                if (q.family == NT_PASS) call.no_scaled_table = true; else call.no_r64 = true;
+                r = make_ntt_route(fld, knobs(), call);
+                i = ~0u;                                            // (again from the first table of the new route)
+            }
+        }
+        const size_t cols = r.cols;
+        with_dif_inv(r.gs, r.inverse, [&](auto DIF, auto INV) {
+            constexpr bool dif = decltype(DIF)::value, inv = decltype(INV)::value;
+            for (unsigned i = 0; i < r.nsteps; i++) {
+                const ntt_step& s = r.steps[i];
+                const dim3 grid(s.gx, s.gy), block(s.block);
+                auto t = [&](signed char k) { return k < 0 ? (const F*)nullptr : tab[k]; };
+                switch (s.kernel) {
+                case NK_BITREV: case NK_BITREV_TILED: case NK_BITREV_TILED_VEC:
+                    launch_bitrev(s, d, lg, col_stride, stream);
+                    break;
+                case NK_COSET:
+                    hipLaunchKernelGGL(k_coset<F>, grid, block, 0, stream, d, G, s.bitrev, col_stride);
+                    break;
+                case NK_SMALL: {
+                    auto go = [&](auto LGC) {
+                        hipLaunchKernelGGL((k_ntt_small<F, inv, decltype(LGC)::value>), grid, block, s.lds, stream, d, T, G, s.flags, col_stride);
+                    };
+                    if constexpr (sizeof(F) <= 8) {
+                        switch (s.LGC) {
+                            case 8:  go(uint_c<8>()); break;
+                            case 9:  go(uint_c<9>()); break;
+                            case 10: go(uint_c<10>()); break;
+                            case 11: go(uint_c<11>()); break;
+                            default: go(uint_c<0>()); break;
+                        }
+                    } else
+                        go(uint_c<0>());
+                    break;
+                }
+                case NK_SMALL_PACKED: {
+                    auto go = [&](auto LG) {
+                        hipLaunchKernelGGL((k_ntt_small_packed<F, inv, decltype(LG)::value>), grid, block, 0, stream, d, T, G, s.flags, col_stride, cols);
+                    };
+                    switch (s.LG) {
+                        case 1: go(uint_c<1>()); break;
+                        case 2: go(uint_c<2>()); break;
+                        case 3: go(uint_c<3>()); break;
+                        case 4: go(uint_c<4>()); break;
+                        case 5: go(uint_c<5>()); break;
+                        default: go(uint_c<6>()); break;
+                    }
+                    break;
+                }
+                case NK_PASS: case NK_PASS_LAT: {
+                    ntt_pass P = s.pass;
+                    P.crow = t(s.crow);
+                    if (r.r64) { P.cg_lo = G.lo; P.cg_hi = G.hi; P.cg_h = G.h; }        // (a folded coset transform)
+                    T.pass_tw = t(s.pass_tw);
+                    if (s.kernel == NK_PASS_LAT) {
+                        if constexpr (!R64) hipLaunchKernelGGL((k_ntt_pass_lat<F, dif, inv>), grid, block, s.lds, stream, d, T, P, col_stride);
+                        break;
+                    }
+                    auto go = [&](auto R1, auto R2) {
+                        auto* fn = k_ntt_pass<F, dif, inv, decltype(R1)::value, decltype(R2)::value>;
+                        if (s.lds > 65536) HIP_OK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds));
+                        hipLaunchKernelGGL(fn, grid, block, s.lds, stream, d, T, P, col_stride);
+                    };
+#define SPPARK_NTT_GO(R1, R2) go(uint_c<R1>(), uint_c<R2>())
+                    if constexpr (sizeof(F) <= 8) { SPPARK_NTT_DISPATCH_S(P.S, SPPARK_NTT_GO); }       // (the instances that exist: k_ntt_pass.hip)
+                    else                          { SPPARK_NTT_DISPATCH_S4(P.S, SPPARK_NTT_GO); }
+#undef SPPARK_NTT_GO
+                    break;
+                }
+                case NK_NTT6: case NK_NTT12: case NK_NTT12_LDE:
+                    if constexpr (R64) {
+                        ntt_r64_args<F> A{T.inner, t(s.tw), t(s.t1), t(s.t2), s.lg_cur, t(s.cz)};
+                        if (s.lde_out) { A.out = lde.out; A.aux_stride = n; }
+                        if (s.kernel == NK_NTT12_LDE) {
+                            const table_set tg = tables(gpu.hip_id, lde.lg_domain, 0, stream);
+                            A.lde_src = lde.src; A.lde_glo = tg.glo; A.lde_ghi = tg.ghi; A.lde_gh = tg.h;
+                            A.lde_lgd = lde.lg_domain; A.lde_lgb = lde.lg_blowup; A.aux_stride = (size_t)1 << lde.lg_domain;
+                            hipLaunchKernelGGL((k_ntt12<F, false, false, true>), grid, block, s.lds, stream, d, A, col_stride);
+                        } else if (s.kernel == NK_NTT6) hipLaunchKernelGGL((k_ntt6<F, dif, inv>), grid, block, s.lds, stream, d, A, col_stride);
+                        else hipLaunchKernelGGL((k_ntt12<F, dif, inv>), grid, block, s.lds, stream, d, A, col_stride);
+                    }
+                    break;
+                case NK_LDE_SPREAD:
+                    lde_spread(gpu, d, lde.src, lde.lg_domain, lde.lg_blowup, true, stream, cols, col_stride, s.spread_in_stride);
+                    break;
+                case NK_COPY_OUT:
+                    copy_cols(lde.out, n, d, col_stride, n, cols, stream);
+                    break;
+                default: break;
+                }
+            }
+        });
+        HIP_OK(hipGetLastError());
     }
+
+public:
+    // columns one launch of run() covers (ntt_route.hpp ntt_launch_cols)
+    size_t launch_cols(const gpu_info& gpu, unsigned lg)
+    {   return ntt_launch_cols(knobs(), lg, (size_t)std::max(gpu.prop.maxGridSize[1], 1));   }
     // |batch| columns of |n| elements from src (src_stride apart) to dst (dst_stride apart), device to device
     static void copy_cols(F* dst, size_t dst_stride, const F* src, size_t src_stride, size_t n, size_t batch, hipStream_t stream)
     {
@@ -538,24 +372,12 @@ public:
         else HIP_OK(hipMemcpy2DAsync(dst, dst_stride * sizeof(F), src, src_stride * sizeof(F), n * sizeof(F), batch, hipMemcpyDeviceToDevice, stream));
     }
 
-    // in-place bit-reversal permutation (NN and RR orders; ntt/ntt.cuh:44-79)
+    // in-place bit-reversal permutation (NN and RR orders; ntt/ntt.cuh:44-79): 16-byte accesses for the single-word fields
+    // where every column starts 16-byte aligned (ntt_route.hpp ntt_route_bitrev)
     static void bit_reverse(F* d, unsigned lg, hipStream_t stream, size_t batch = 1, size_t col_stride = 0)
     {
-        constexpr unsigned TB = bitrev_tile_bits<F>::value;
-        const size_t n = (size_t)1 << lg;
-        if (lg >= 2 * TB + 1) {
-            size_t lds = 2 * (((size_t)(1u << TB) + 1) << TB) * sizeof(F);
-            // 16-byte accesses for the single-word fields (any 16-byte aligned buffer; a view at an odd element offset
-            // takes the element-wise tiles) -- in a batch, only when every column starts 16-byte aligned
-            bool vec = false;
-            if constexpr (sizeof(F) <= 8) vec = ((uintptr_t)d & 15) == 0 && (batch == 1 || ((col_stride * sizeof(F)) & 15) == 0);
-            if constexpr (sizeof(F) <= 8) {
-                if (vec) hipLaunchKernelGGL((k_bitrev_tiled_vec<F, TB>), dim3((unsigned)(n >> (2 * TB)), (unsigned)batch), dim3(256), lds, stream, d, lg, col_stride);
-            }
-            if (!vec) hipLaunchKernelGGL((k_bitrev_tiled<F, TB>), dim3((unsigned)(n >> (2 * TB)), (unsigned)batch), dim3(256), lds, stream, d, lg, col_stride);
-        } else {
-            hipLaunchKernelGGL(k_bitrev<F>, dim3((unsigned)((n + 255) / 256), (unsigned)batch), dim3(256), 0, stream, d, lg, col_stride);
-        }
+        const bool aligned16 = ((uintptr_t)d & 15) == 0 && (batch == 1 || ((col_stride * sizeof(F)) & 15) == 0);
+        launch_bitrev(ntt_route_bitrev(ntt_field_of<F>(), lg, batch, aligned16), d, lg, col_stride, stream);
     }
 
     // d_inout[idx] *= g^(rev(idx))   (NTT::LDE_powers(stream, d_inout, lg), ntt/ntt.cuh:352-356)

@@ -36,7 +36,7 @@ namespace sppark_amd {
 
 // what k_ntt_small (whole transforms by one work-group, below) is compiled for: 2^11 elements of a single-word field (1024
 // lanes, eleven twiddles in registers), 2^10 of a 256-bit one (512 lanes).  What the driver USES by default is
-// ntt_engine::small_max_lg().
+// ntt_knobs::small_max (ntt_route.hpp).
 template<class F> struct ntt_small_cap { static constexpr unsigned value = sizeof(F) > 8 ? 10 : 11; };
 // entries of ntt_tables::inner: the levels R <= 8 of the register radices and, for k_ntt_small, R <= its cap
 template<class F> struct ntt_inner_entries { static constexpr unsigned value = 2u << (ntt_small_cap<F>::value > 8 ? ntt_small_cap<F>::value : 8); };

@@ -39,6 +39,12 @@ def _emu(feature):
     L.emu_ntt_coset_fold.restype = None
     L.emu_ntt_coset_mode.argtypes = [ctypes.c_uint, ctypes.c_int, ctypes.c_int]
     L.emu_ntt_coset_mode.restype = ctypes.c_uint
+    L.emu_ntt_refuse.argtypes = [ctypes.c_uint, ctypes.c_uint]
+    L.emu_ntt_refuse.restype = None
+    L.emu_ntt_route.argtypes = [ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint), ctypes.c_uint]
+    L.emu_ntt_route.restype = ctypes.c_uint
+    L.emu_ntt_knobs.argtypes = [ctypes.POINTER(ctypes.c_uint)]
+    L.emu_ntt_knobs.restype = None
     return L
 
 
@@ -165,8 +171,17 @@ def test_ntt_radix64_plan_on_host(oracle, field, feature):
             z = x.copy()
             L.emu_ntt(z.ctypes.data, lg, 1, 0, 0, 256)
             assert (z == f(x, 1, 0, 0)).all()
+            # the routes the driver falls back to when the device has no room for a table (ntt_call::no_r64: without the
+            # radix-64 plan; no_scaled_table: 1/n by the last pass instead of a table), inverse NR at 2^13
+            if field == "gl64" and lg == 13:
+                L.emu_ntt_plan(12, 20)
+                for no_r64, no_scaled in ((1, 0), (1, 1), (0, 1)):
+                    L.emu_ntt_refuse(no_r64, no_scaled)
+                    z = x.copy()
+                    L.emu_ntt(z.ctypes.data, lg, 1, 1, 0, 256)
+                    assert (z == f(x, 1, 1, 0)).all(), (no_r64, no_scaled)
     finally:
-        L.emu_ntt_plan(12, 20)
+        L.emu_ntt_plan(12, 20); L.emu_ntt_refuse(0, 0)
 
 
 @pytest.mark.parametrize("field,feature", [("gl64", "GOLDILOCKS"), ("bb31", "BABY_BEAR")])

@@ -160,9 +160,10 @@ def _kernel(name):
     return re.sub(r"^void ", "", name).replace("sppark_amd::", "")
 
 
-def extract(db_path, out_path, meta_path):
+def dispatch_rows(db_path):
+    """(columns, rows) of the profiler's dispatch table in issue order: a row is (kernel as _kernel() names it, grid x, grid y,
+    work-group size[, LDS bytes]); also what tools/gpu_ntt_launch_trace.py cuts into cases"""
     import sqlite3
-    meta = json.load(open(meta_path))
     db = sqlite3.connect(db_path)
     tabs = [r[0] for r in db.execute("select name from sqlite_master where type in ('table','view')")]
     kd = [t for t in tabs if t.startswith("rocpd_kernel_dispatch")][0]
@@ -177,10 +178,15 @@ def extract(db_path, out_path, meta_path):
     rows = db.execute("select s.%s, %s from %s d join %s s on d.kernel_id = s.id order by d.%s"
                       % (name_col, ", ".join("d." + c for c in cols), kd, ks, "dispatch_id" if "dispatch_id" in have else "start")).fetchall()
     short = {n: _kernel(n) for n in {r[0] for r in rows}}
-    rows = [(short[r[0]],) + tuple(int(v) for v in r[1:]) for r in rows]
+    return cols, [(short[r[0]],) + tuple(int(v) for v in r[1:]) for r in rows]
+
+
+def extract(db_path, out_path, meta_path):
+    meta = json.load(open(meta_path))
+    cols, rows = dispatch_rows(db_path)
     marks = [i for i, r in enumerate(rows) if r[0].startswith("k_breakdown")]
     want = sum(c["markers"] for c in meta["cases"])
-    assert len(marks) == want, (len(marks), want, sym, have, sorted({r[0] for r in rows})[:40])
+    assert len(marks) == want, (len(marks), want, sorted({r[0] for r in rows})[:40])
     names, out, m = [], [], 0
     for c in meta["cases"]:
         lo = marks[m]; m += c["markers"]

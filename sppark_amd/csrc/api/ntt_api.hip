@@ -248,3 +248,4 @@ SPPARK_FFI size_t sppark_ntt_batch_launch_cols(size_t device_id, uint32_t lg_dom
 }
 
 #include "poly_api.hpp"
+#include "field_api.hpp"

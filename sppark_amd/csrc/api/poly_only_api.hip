@@ -16,3 +16,4 @@ template<class Fn> static RustError guarded(Fn&& fn)
 }
 
 #include "poly_api.hpp"
+#include "field_api.hpp"

@@ -30,6 +30,26 @@ template<class P> struct alignas(16) fr256_dev : mont_dev<P> {
     SPPARK_DEVFN static constexpr bool root_neg(unsigned, unsigned) { return false; }
     SPPARK_DEVFN static void bfly(const fr256_dev& a, const fr256_dev& b, fr256_dev& s, fr256_dev& d)
     {   fr256_dev t = a - b; s = a + b; d = t;   }
+    // (is_zero(): mont_dev's)
+    // a^(p-2) = 1/a for a != 0, Montgomery in and out: square-and-multiply over the words of the modulus, from the
+    // top bit down (as montx_dev::inverse()).  ~NBITS squares + NBITS/2 products: once per call of the field-vector
+    // inverse (poly/inv_kernels.hpp k_inv_spine), never per element.
+    SPPARK_DEVFN fr256_dev inverse() const
+    {
+        base r = base::one();
+        bool started = false;
+        #pragma unroll 1
+        for (int w = base::N - 1; w >= 0; w--) {
+            u32 e = 0, borrow = 2;                              // word w of p - 2 (a modulus may end in ...00000001)
+            for (int k = 0; k <= w; k++) { e = P::MOD[k] - borrow; borrow = P::MOD[k] < borrow ? 1u : 0u; }
+            #pragma unroll 1
+            for (int b = 31; b >= 0; b--) {
+                if (started) r = r.sqr();
+                if ((e >> b) & 1u) { r = started ? r * static_cast<const base&>(*this) : static_cast<const base&>(*this); started = true; }
+            }
+        }
+        return r;
+    }
 };
 
 } // namespace sppark_amd

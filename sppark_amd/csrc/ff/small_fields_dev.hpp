@@ -22,6 +22,8 @@
 
 namespace sppark_amd {
 
+template<class F> SPPARK_DEVFN F field_pow(F b, u64 e);          // (defined below the field classes)
+
 struct gl64_dev {
     static constexpr u64 MOD = 0xffffffff00000001ULL;
     static constexpr unsigned TWO_ADICITY = 32;
@@ -41,6 +43,8 @@ struct gl64_dev {
     SPPARK_DEVFN static gl64_dev one() { return from_raw(1); }
     SPPARK_DEVFN static gl64_dev top_root() { return from_raw(TOP_ROOT); }
     SPPARK_DEVFN static gl64_dev group_gen() { return from_raw(GROUP_GEN); }
+    SPPARK_DEVFN bool is_zero() const { return v == 0; }
+    SPPARK_DEVFN gl64_dev inverse() const { return field_pow(*this, MOD - 2); }        // a^(p-2); a != 0
 
     // Carry-generating VALU ops are the expensive ones on gfx950 (v_add_co/v_addc_co
     // issue at half the rate of plain 32-bit ops, and hipcc's u64 compare+select
@@ -368,6 +372,8 @@ struct bb31_dev {
     SPPARK_DEVFN static bb31_dev one() { return from_raw(ONE); }
     SPPARK_DEVFN static bb31_dev top_root() { return from_raw(TOP_ROOT); }
     SPPARK_DEVFN static bb31_dev group_gen() { return from_raw(GROUP_GEN) * from_raw(RR); }    // in Montgomery form
+    SPPARK_DEVFN bool is_zero() const { return v == 0; }
+    SPPARK_DEVFN bb31_dev inverse() const { return field_pow(*this, (u64)MOD - 2); }   // a^(p-2), Montgomery in and out; a != 0
 
     // Conditional corrections as an unsigned MINIMUM: x in [0, 2p) -> min(x, x - p) (x < p: x - p wraps above x), and
     // for a difference d = a - b (mod 2^32) -> min(d, d + p) (a < b: d is huge and d + p wraps to the residue).  Two
@@ -408,6 +414,8 @@ struct mrs31_dev {
     u32 v;                                                      // [0, p)
     SPPARK_DEVFN static mrs31_dev from_raw(u32 x) { mrs31_dev r; r.v = x; return r; }
     SPPARK_DEVFN static mrs31_dev one() { return from_raw(1); }
+    SPPARK_DEVFN bool is_zero() const { return v == 0; }
+    SPPARK_DEVFN mrs31_dev inverse() const { return field_pow(*this, (u64)MOD - 2); }  // a^(p-2); a != 0
     SPPARK_DEVFN friend mrs31_dev operator+(mrs31_dev a, mrs31_dev b)
     {   u32 s = a.v + b.v; s -= (s >= MOD) ? MOD : 0; return from_raw(s);   }
     SPPARK_DEVFN friend mrs31_dev operator-(mrs31_dev a, mrs31_dev b)
@@ -457,6 +465,28 @@ struct alignas(16) bb31_4_dev {
         }
         bb31_4_dev r;
         r.c[0] = lo[0] + beta * hi[0]; r.c[1] = lo[1] + beta * hi[1]; r.c[2] = lo[2] + beta * hi[2]; r.c[3] = lo[3];
+        return r;
+    }
+    SPPARK_DEVFN bool is_zero() const { return (c[0].v | c[1].v | c[2].v | c[3].v) == 0; }
+    // 1/a through two norms, for a != 0.  With y = x^2 (y^2 = beta) the field is K(x), K = F_p(y), and
+    // a = A + B x with A = c0 + c2 y, B = c1 + c3 y in K.  Then a * (A - B x) = A^2 - y B^2 =: n0 + n1 y in K,
+    // (n0 + n1 y) * (n0 - n1 y) = n0^2 - beta n1^2 =: d in F_p, and 1/a = (A - B x) * (n0 - n1 y) / d:
+    // one bb31_dev inverse.  (In K: (u + v y)(s + t y) = (u s + beta v t) + (u t + v s) y, and
+    // y (u + v y) = beta v + u y.)
+    SPPARK_DEVFN bb31_4_dev inverse() const
+    {
+        const bb31_dev beta = bb31_dev::from_raw(BETA);
+        const bb31_dev a0 = c[0], a1 = c[2], b0 = c[1], b1 = c[3];                     // A = a0 + a1 y, B = b0 + b1 y
+        const bb31_dev bb0 = b0 * b0 + beta * (b1 * b1), bb1 = b0 * b1 + b0 * b1;      // B^2
+        const bb31_dev n0 = a0 * a0 + beta * (a1 * a1) - beta * bb1;                   // A^2 - y B^2
+        const bb31_dev n1 = a0 * a1 + a0 * a1 - bb0;
+        const bb31_dev di = (n0 * n0 - beta * (n1 * n1)).inverse();
+        const bb31_dev k0 = n0 * di, k1 = bb31_dev::from_raw(0) - n1 * di;             // 1 / (n0 + n1 y) = k0 + k1 y
+        bb31_4_dev r;
+        r.c[0] = a0 * k0 + beta * (a1 * k1);                                           //  A * k
+        r.c[2] = a0 * k1 + a1 * k0;
+        r.c[1] = bb31_dev::from_raw(0) - (b0 * k0 + beta * (b1 * k1));                 // -B * k
+        r.c[3] = bb31_dev::from_raw(0) - (b0 * k1 + b1 * k0);
         return r;
     }
 };

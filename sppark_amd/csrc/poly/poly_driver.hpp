@@ -1,8 +1,10 @@
 // Host driver of the polynomial primitives (polynomial/prefix_op.cuh:324-396,
 // polynomial/evaluate.cuh:307-412, polynomial/div_by_x_minus_z.cuh:447-486): three plain
-// launches per scan on one stream, scratch from the per-library pool (util/runtime.hpp).
+// launches per scan on one stream, scratch from the per-library pool (util/runtime.hpp); and of the field-vector inverse
+// (ff/batch_inversion.hpp; poly/inv_kernels.hpp), which has the same three-launch shape.
 #pragma once
 #include "poly_kernels.hpp"
+#include "inv_kernels.hpp"
 #include "../util/runtime.hpp"
 
 namespace sppark_amd {
@@ -54,6 +56,25 @@ template<class F> struct poly_engine {
         if (rotate) scan<op_horner<F>, true>(d_inout, d_inout, len, op, stream);
         else        scan<op_horner<F>, false>(d_inout, d_inout, len, op, stream);
         zp.done();                                      // (scan() synchronised the stream)
+    }
+
+    // out[i] = 1 / den[i], or num[i] / den[i] when d_num is not null; 0 where den[i] == 0 (ff/batch_inversion.hpp).
+    // d_out may alias d_den or d_num.  One field inversion per call (k_inv_spine), whatever len is.
+    static void inverse(F* d_out, const F* d_num, const F* d_den, size_t len, hipStream_t stream)
+    {
+        if (len == 0) return;
+        const size_t ntiles = (len + TILE - 1) / TILE;
+        if (ntiles > 0x7fffffffu) HIP_OK(hipErrorInvalidValue);
+        scratch agg(2 * ntiles * sizeof(F));            // [tile products -> their inverses][the spine's running products]
+        F* d_agg = (F*)agg.p;
+        const size_t lds = 2 * POLY_NT * sizeof(F);
+        hipLaunchKernelGGL(k_inv_reduce<F>, dim3((unsigned)ntiles), dim3(POLY_NT), lds, stream, d_agg, d_den, len);
+        hipLaunchKernelGGL(k_inv_spine<F>, dim3(1), dim3(POLY_NT), lds, stream, d_agg, d_agg + ntiles, ntiles);
+        if (d_num) hipLaunchKernelGGL((k_inv_apply<F, true>), dim3((unsigned)ntiles), dim3(POLY_NT), lds, stream, d_out, d_num, d_den, (const F*)d_agg, len);
+        else       hipLaunchKernelGGL((k_inv_apply<F, false>), dim3((unsigned)ntiles), dim3(POLY_NT), lds, stream, d_out, d_num, d_den, (const F*)d_agg, len);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipStreamSynchronize(stream));           // the scratch goes back to the pool with this frame
+        agg.done();
     }
 
     // ret[j] = sum_i coeffs[i] * x[j]^i for j < n; all device pointers

@@ -178,6 +178,10 @@ def load(name):
         L.sppark_poly_evaluate.restype = _Error
         L.sppark_div_by_x_minus_z.argtypes = [sz, vp, sz, vp, ci, vp]
         L.sppark_div_by_x_minus_z.restype = _Error
+        L.sppark_field_inverse.argtypes = [sz, vp, vp, sz, vp]                   # include/sppark_amd_field.h
+        L.sppark_field_inverse.restype = _Error
+        L.sppark_field_divide.argtypes = [sz, vp, vp, vp, sz, vp]
+        L.sppark_field_divide.restype = _Error
     _LIBS[name] = L
     return L
 

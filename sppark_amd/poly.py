@@ -1,6 +1,7 @@
 """Polynomial primitives: host API over sppark_prefix_op / sppark_poly_evaluate /
 sppark_div_by_x_minus_z (the reference offers them as C++ templates only:
-polynomial/prefix_op.cuh:324-396, evaluate.cuh:307-412, div_by_x_minus_z.cuh:447-486).
+polynomial/prefix_op.cuh:324-396, evaluate.cuh:307-412, div_by_x_minus_z.cuh:447-486), and the field-vector
+inverse and quotient over sppark_field_inverse / sppark_field_divide (ff/batch_inversion.hpp, a host template there).
 Buffers are numpy arrays or torch tensors (host or device) of field elements in the wire
 format of the chosen library (gl64: canonical u64; bb31: Montgomery u32; bls12_381 / bn254:
 the curve's scalar field, 4 x u64 Montgomery)."""
@@ -48,3 +49,26 @@ def div_by_x_minus_z(inout, z, rotate=False, field="gl64", device_id=0, stream=N
     p, _k1 = ffi.as_pointer(inout); pz, _k2 = ffi.as_pointer(z)
     ffi.check(L, L.sppark_div_by_x_minus_z(device_id, p, _count(inout, field), pz, int(rotate), stream))
     return inout
+
+
+def inverse(out, inp, field="gl64", device_id=0, stream=None):
+    """out[i] = 1 / inp[i], and 0 where inp[i] == 0 (the reference's ff/batch_inversion.hpp, on the device:
+    one field inversion per call); out may be inp itself.  Elements must be canonical."""
+    L = ffi.load(field)
+    n = _count(inp, field)
+    if _count(out, field) != n:
+        raise ValueError("length mismatch")
+    po, _k1 = ffi.as_pointer(out); pi, _k2 = ffi.as_pointer(inp)
+    ffi.check(L, L.sppark_field_inverse(device_id, po, pi, n, stream))
+    return out
+
+
+def divide(out, num, den, field="gl64", device_id=0, stream=None):
+    """out[i] = num[i] / den[i], and 0 where den[i] == 0; out may be num or den."""
+    L = ffi.load(field)
+    n = _count(den, field)
+    if _count(out, field) != n or _count(num, field) != n:
+        raise ValueError("length mismatch")
+    po, _k1 = ffi.as_pointer(out); pn, _k2 = ffi.as_pointer(num); pd, _k3 = ffi.as_pointer(den)
+    ffi.check(L, L.sppark_field_divide(device_id, po, pn, pd, n, stream))
+    return out

@@ -182,6 +182,16 @@ def load(name):
         L.sppark_field_inverse.restype = _Error
         L.sppark_field_divide.argtypes = [sz, vp, vp, vp, sz, vp]
         L.sppark_field_divide.restype = _Error
+        for fn in (L.sppark_field_add, L.sppark_field_sub, L.sppark_field_mul, L.sppark_field_scale):     # include/sppark_amd_arith.h
+            fn.argtypes = [sz, vp, vp, vp, sz, vp]
+            fn.restype = _Error
+        L.sppark_field_mul_sub.argtypes = [sz, vp, vp, vp, vp, vp, sz, vp]
+        L.sppark_field_mul_sub.restype = _Error
+    if name in NTT_FIELDS or name in CURVES:
+        L.sppark_poly_product.argtypes = [sz, vp, vp, sz, vp, sz, vp]
+        L.sppark_poly_product.restype = _Error
+        L.sppark_poly_vanishing_quotient.argtypes = [sz, vp, vp, vp, vp, ctypes.c_uint32, vp]
+        L.sppark_poly_vanishing_quotient.restype = _Error
     _LIBS[name] = L
     return L
 

@@ -505,6 +505,63 @@ SPPARK_FFI void sppark_msm_plan_sort(const sppark_msm_ctx* ctx, size_t npoints, 
     out[0] = p.nslabs; out[1] = p.slab_sz; out[2] = p.IB; out[3] = p.SH; out[4] = p.NG; out[5] = p.G; out[6] = p.K1;
     out[7] = ctx->impl.piece_tree_cmax(p);
 }
+// ---- short scalars (include/sppark_amd_short.h): the caller declares the bit length, only its windows run -------
+// (the contract is checked first -- msm_t::check_short --: a refused call selects no device and reads nothing)
+SPPARK_FFI RustError sppark_msm_invoke_bits(sppark_msm_ctx* ctx, void* out, const void* points, size_t npoints,
+                                            const void* scalars, unsigned scalar_bits, size_t scalar_stride, size_t ffi_affine_sz)
+{
+    store_inf(out);
+    return guarded([&] {
+        point_t r;
+        ctx->impl.invoke_short(r, points, npoints, scalars, scalar_bits, scalar_stride, ffi_affine_sz);
+        store_point(out, r);
+    });
+}
+SPPARK_FFI RustError sppark_msm_reserve_bits(sppark_msm_ctx* ctx, size_t npoints, size_t ffi_affine_sz, int host_points, int host_scalars,
+                                             unsigned scalar_bits, size_t scalar_stride)
+{
+    return guarded([&] {
+        msm_impl::check_short(scalar_bits, scalar_stride, nullptr);
+        ctx->impl.reserve_for(npoints, ffi_affine_sz, host_points, host_scalars, msm_impl::scalar_form(scalar_bits, scalar_stride));
+    });
+}
+SPPARK_FFI void sppark_msm_plan_bits(const sppark_msm_ctx* ctx, size_t npoints, unsigned scalar_bits, unsigned out[8])
+{
+    for (int i = 0; i < 8; i++) out[i] = 0;
+    if (scalar_bits == 0 || scalar_bits > msm_impl::SHORT_BITS_MAX) return;
+    msm_plan p = ctx->impl.plan_for(npoints, scalar_bits);
+    out[0] = p.wbits; out[1] = p.nwins; out[2] = p.NB; out[3] = p.L; out[4] = p.NA; out[5] = p.LB; out[6] = p.F; out[7] = p.K;
+}
+SPPARK_FFI RustError mult_pippenger_inf_bits(void* out, const void* points, size_t npoints, const void* scalars,
+                                             unsigned scalar_bits, size_t scalar_stride, size_t ffi_affine_sz)
+{
+    store_inf(out);
+    return guarded([&] {
+        msm_impl::check_short(scalar_bits, scalar_stride, scalars);
+        borrowed<msm_impl> msm(-1);
+        if (is_device_pointer(points) || is_device_pointer(scalars)) HIP_OK(hipDeviceSynchronize());     // (as one_shot())
+        point_t r;
+        msm->invoke_short(r, points, npoints, scalars, scalar_bits, scalar_stride, ffi_affine_sz);
+        store_point(out, r);
+    });
+}
+#ifndef SPPARK_NO_G2
+SPPARK_FFI RustError mult_pippenger_fp2_inf_bits(void* out, const void* points, size_t npoints, const void* scalars,
+                                                 unsigned scalar_bits, size_t scalar_stride, size_t ffi_affine_sz)
+{
+    memset(out, 0, sizeof(point2_t));
+    return guarded([&] {
+        msm2_impl::check_short(scalar_bits, scalar_stride, scalars);
+        borrowed<msm2_impl> msm(-1);
+        msm->tune.g2_coop = g2_path.load(std::memory_order_relaxed);
+        if (is_device_pointer(points) || is_device_pointer(scalars)) HIP_OK(hipDeviceSynchronize());
+        point2_t r;
+        msm->invoke_short(r, points, npoints, scalars, scalar_bits, scalar_stride, ffi_affine_sz);
+        memcpy(out, &r, sizeof(r));
+    });
+}
+#endif
+
 SPPARK_FFI RustError sppark_msm_tune_records(sppark_msm_ctx* ctx, unsigned records)
 {   return guarded([&] { if (records > 2) throw hip_error(-(int)hipErrorInvalidValue, "tune_records"); ctx->impl.tune.records = records; });   }
 // window groups the context would use for |npoints|

@@ -302,20 +302,42 @@ public:
         if (blob) { (void)hipFree(blob); blob = nullptr; blob_sz = 0; }
         if (stage) { (void)hipFree(stage); stage = nullptr; stage_sz = 0; }
     }
-    msm_plan plan_for(size_t npoints) const { return make_plan(npoints, FRp::NBITS, tune); }
+    // ---- the scalars of one call: full width (FRp::NBITS bits in SCALAR_BYTES, folded below r/2 by k_breakdown), or SHORT:
+    // |bits| declared significant bits, |stride| bytes apart (include/sppark_amd_short.h; k_breakdown_short) ----
+    struct scalar_form {
+        unsigned bits;                                  // 0 = full width
+        size_t stride;
+        scalar_form() : bits(0), stride(SCALAR_BYTES) {}
+        scalar_form(unsigned b, size_t s) : bits(b), stride(s) {}
+        unsigned plan_bits() const { return bits ? bits + 1 : (unsigned)FRp::NBITS; }    // (+ 1: the bit that closes the signed recoding)
+    };
+    static constexpr unsigned SHORT_BITS_MAX = FRp::NBITS - 2;
+    // the contract of a short call; nothing but the arguments is looked at (no device, no memory)
+    static void check_short(unsigned bits, size_t stride, const void* scalars)
+    {
+        const bool ok = bits >= 1 && bits <= SHORT_BITS_MAX && (stride & 3) == 0 && stride >= 4 * (size_t)((bits + 31) / 32) && stride <= 32
+                        && ((size_t)scalars & (stride == 4 || stride == 8 || stride == 16 ? stride - 1 : 3)) == 0;
+        if (!ok)
+            throw hip_error(-(int)hipErrorInvalidValue, "short scalars: scalar_bits must be 1.." + std::to_string(SHORT_BITS_MAX)
+                            + ", scalar_stride a multiple of 4 in [4 * ceil(scalar_bits / 32), 32], the scalars aligned to a stride of 4, 8 or 16 "
+                              "bytes and to 4 bytes otherwise: invalid argument");
+    }
+
+    msm_plan plan_for(size_t npoints, unsigned short_bits = 0) const
+    {   return make_plan(npoints, scalar_form(short_bits, 0).plan_bits(), tune);   }
 
     // Size the scratch for |npoints| ahead of time (so a timed invoke does not allocate).
-    void reserve_for(size_t npoints, size_t ffi_affine_sz, bool host_points, bool host_scalars)
+    void reserve_for(size_t npoints, size_t ffi_affine_sz, bool host_points, bool host_scalars, const scalar_form& sf = scalar_form())
     {
         HIP_OK(hipSetDevice(gpu->hip_id));
-        size_t chunk = choose_chunk(npoints, (host_points ? ffi_affine_sz : 0) + (host_scalars ? SCALAR_BYTES : 0));
+        size_t chunk = choose_chunk(npoints, (host_points ? ffi_affine_sz : 0) + (host_scalars ? sf.stride : 0), sf.plan_bits());
         // as invoke(): one plan per chunk length, scratch for the largest layout
         const std::vector<size_t> cb = chunk_bounds(npoints, chunk);
         size_t need = 0;
-        for (size_t c = 0; c + 1 < cb.size(); c++) need = std::max(need, make_layout(make_plan(cb[c + 1] - cb[c], FRp::NBITS, tune), true).total);
+        for (size_t c = 0; c + 1 < cb.size(); c++) need = std::max(need, make_layout(make_plan(cb[c + 1] - cb[c], sf.plan_bits(), tune), true).total);
         reserve(need);
         if (host_points || host_scalars)
-            reserve_stage(2 * (align_up(host_points ? chunk * ffi_affine_sz : 0) + align_up(host_scalars ? chunk * SCALAR_BYTES : 0)));
+            reserve_stage(2 * (align_up(host_points ? chunk * ffi_affine_sz : 0) + align_up(host_scalars ? chunk * sf.stride : 0)));
     }
 
     // Private stream only: wait for everything queued so far on the legacy default stream, where
@@ -439,7 +461,8 @@ private:
     // points per chunk.  |stage_per_point|: bytes of host-resident input per point that have to be
     // copied (0: everything is on the device); chunking then overlaps the copies with the
     // arithmetic.  Device-resident inputs are chunked only when the scratch would not fit.
-    size_t choose_chunk(size_t n, size_t stage_per_point) const
+    // |plan_bits|: the scalar bits the chunks are planned for (scalar_form::plan_bits)
+    size_t choose_chunk(size_t n, size_t stage_per_point, unsigned plan_bits = FRp::NBITS) const
     {
         size_t chunk = n;
         if (tune.chunk) chunk = std::min(n, std::max<size_t>(tune.chunk, 1));
@@ -451,13 +474,13 @@ private:
             chunk = std::min<size_t>(std::max<size_t>(n / 4, (size_t)1 << 20), (size_t)1 << 24);
         }
         auto need = [&](size_t c) {
-            return make_layout(make_plan(c, FRp::NBITS, tune), true).total + 2 * c * stage_per_point + 1024;
+            return make_layout(make_plan(c, plan_bits, tune), true).total + 2 * c * stage_per_point + 1024;
         };
         size_t limit = tune.max_scratch;
         if (!limit) {
             // already reserved (both allocations, each on its own: the scratch blob and the staging sets
             // are separate hipMallocs): no driver query
-            const bool blob_ok = make_layout(make_plan(chunk, FRp::NBITS, tune), true).total <= blob_sz;
+            const bool blob_ok = make_layout(make_plan(chunk, plan_bits, tune), true).total <= blob_sz;
             const bool stage_ok = stage_per_point == 0 || 2 * (chunk * stage_per_point + 512) <= stage_sz;  // two sets, each of two 256-byte aligned parts
             if (blob_ok && stage_ok) return chunk;
             size_t free_b = 0, total_b = 0;
@@ -491,7 +514,7 @@ private:
     // |fb_n| != 0: fixed-base mode -- |p| describes ONE window over fb_nwins * fb_n entries; the digits come from the
     // fb_n scalars cut into fb_nwins real windows (digit (w, i) is entry w * fb_n + i of the one window)
     void sort_group(hipStream_t ss, const msm_plan& p, const layout& l, unsigned b, unsigned w0, unsigned wn,
-                    const u32* d_scalars, bool mont, unsigned fb_n = 0, unsigned fb_nwins = 0)
+                    const u32* d_scalars, bool mont, unsigned fb_n = 0, unsigned fb_nwins = 0, const scalar_form& form = scalar_form())
     {
         u32* digits = (u32*)(blob + l.digits[b]);
         u32* sorted = (u32*)(blob + l.sorted[b]);
@@ -510,6 +533,16 @@ private:
             unsigned grid = std::min<unsigned>((fb_n + 255) / 256, 256 * 16);
             hipLaunchKernelGGL(k_breakdown<fr_d>, dim3(grid), dim3(256), 0, ss,
                                digits, d_scalars, fb_n, fb_nwins, (unsigned)FRp::NBITS, (int)mont, 0u, fb_nwins);
+        } else if (form.bits) {
+            // short scalars: the plan's nbits is form.bits + 1; instantiated by the words that hold the bits, rounded up to 1, 2, 4, 8
+            const unsigned grid = std::min<unsigned>((p.n + 255) / 256, 256 * 16), sw = (unsigned)(form.stride / 4);
+            const dim3 g(grid), t(256);
+            switch (short_words_pow2((form.bits + 31) / 32)) {
+            case 1:  hipLaunchKernelGGL(k_breakdown_short<1>, g, t, 0, ss, digits, d_scalars, p.n, p.nwins, p.nbits, sw, w0, wn); break;
+            case 2:  hipLaunchKernelGGL(k_breakdown_short<2>, g, t, 0, ss, digits, d_scalars, p.n, p.nwins, p.nbits, sw, w0, wn); break;
+            case 4:  hipLaunchKernelGGL(k_breakdown_short<4>, g, t, 0, ss, digits, d_scalars, p.n, p.nwins, p.nbits, sw, w0, wn); break;
+            default: hipLaunchKernelGGL(k_breakdown_short<8>, g, t, 0, ss, digits, d_scalars, p.n, p.nwins, p.nbits, sw, w0, wn); break;
+            }
         } else {
             unsigned grid = std::min<unsigned>((p.n + 255) / 256, 256 * 16);
             hipLaunchKernelGGL(k_breakdown<fr_d>, dim3(grid), dim3(256), 0, ss,
@@ -583,10 +616,10 @@ private:
     // (|may_defer|: the caller looks at the flag after this MSM -- invoke() with one chunk)
     void enqueue(const msm_plan& p, const layout& l, const unsigned char* d_points, size_t stride, bool preconverted,
                  const u32* d_scalars, bool mont, std_bucket_t* h_out, bool first_timed, unsigned fb_n = 0, unsigned fb_nwins = 0,
-                 bool redo = false, bool may_defer = false)
+                 bool redo = false, bool may_defer = false, const scalar_form& sf = scalar_form())
     {
         msm_call call;
-        call.fb_n = fb_n; call.redo = redo; call.may_defer = may_defer;
+        call.fb_n = fb_n; call.redo = redo; call.may_defer = may_defer; call.short_bits = sf.bits;
         call.convert = INTERNAL && !preconverted;
         call.flagged = !preconverted && stride > 2 * FP_BYTES;
         call.stride = stride; call.aligned16 = ((size_t)d_points & 15) == 0;
@@ -719,7 +752,7 @@ private:
             const unsigned b = multi ? (gseq & 1) : 0, w0 = g * p.wpg, wn = std::min(p.wpg, p.nwins - w0);
             if (g == 0) {
                 // first group: on the main stream, at full width (stream order protects the set)
-                sort_group(stream, p, l, b, w0, wn, d_scalars, mont, fb_n, fb_nwins);
+                sort_group(stream, p, l, b, w0, wn, d_scalars, mont, fb_n, fb_nwins, sf);
                 // (the conversion does not depend on the scalars, but running it on the second stream beside the digit /
                 // sort kernels gains nothing: all of them are memory-bound and share HBM -- 13.4 ms before the accumulation
                 // either way at 2^26, profiles/r04_msm_convert_beside_sort_negative.log; round 2 measured the same)
@@ -729,7 +762,7 @@ private:
                 }
             } else {
                 if (gseq >= 2) HIP_OK(hipStreamWaitEvent(aux, ev_accdone[b], 0));    // the accumulation two groups back has read this set
-                sort_group(aux, p, l, b, w0, wn, d_scalars, mont);
+                sort_group(aux, p, l, b, w0, wn, d_scalars, mont, 0, 0, sf);
                 HIP_OK(hipEventRecord(ev_sorted[b], aux));
                 HIP_OK(hipStreamWaitEvent(stream, ev_sorted[b], 0));
             }
@@ -770,7 +803,8 @@ private:
 
 public:
     // pieces per bucket the piece tree of a small MSM takes (msm_route.hpp piece_tree_cmax), 0 = none
-    unsigned piece_tree_cmax(const msm_plan& p) const { return sppark_amd::piece_tree_cmax(p, tune.sw, 0, FRp::MOD, (unsigned)FRp::N); }
+    unsigned piece_tree_cmax(const msm_plan& p, unsigned short_bits = 0) const
+    {   return sppark_amd::piece_tree_cmax(p, tune.sw, 0, FRp::MOD, (unsigned)FRp::N, short_bits);   }
 private:
 
     // Horner over the window sums (the reference's host-side collect, pippenger.cuh:627-727, is O(256 * windows))
@@ -908,6 +942,23 @@ public:
     // format iff ffi_affine_sz > 2*FP_BYTES.  scalars: SCALAR_BYTES each.
     void invoke(point_t& out, const void* points, size_t npoints, const void* scalars,
                 bool mont, size_t ffi_affine_sz)
+    {   invoke_form(out, points, npoints, scalars, mont, ffi_affine_sz, scalar_form());   }
+
+    // The same over SHORT scalars (include/sppark_amd_short.h): plain integers of |bits| significant bits, |stride| bytes
+    // apart; the result is the MSM of s_i mod 2^bits.  Refused (hipErrorInvalidValue) outside the contract, before the
+    // device is selected or a byte is read.  On a context with fixed-base tables the call runs the ordinary path over the
+    // preloaded points themselves (level 0 of the table), as a call of any other length does.
+    void invoke_short(point_t& out, const void* points, size_t npoints, const void* scalars,
+                      unsigned bits, size_t stride, size_t ffi_affine_sz)
+    {
+        out.set_inf();
+        check_short(bits, stride, scalars);
+        invoke_form(out, points, npoints, scalars, false, ffi_affine_sz, scalar_form(bits, stride));
+    }
+
+private:
+    void invoke_form(point_t& out, const void* points, size_t npoints, const void* scalars,
+                     bool mont, size_t ffi_affine_sz, const scalar_form& sf)
     {
         out.set_inf();
         if (npoints == 0) return;
@@ -921,14 +972,14 @@ public:
         if (scalars == nullptr || ffi_affine_sz < 2 * FP_BYTES) HIP_OK(hipErrorInvalidValue);
         join_default_stream();
         // fixed-base tables cover exactly the preloaded vector: any other length runs the ordinary path on its first level
-        if (preconverted && pre_fb_nwins && npoints == pre_n && tune.chunk == 0 && tune.max_scratch == 0 && fixed_fits(npoints, scalars)) {
+        if (preconverted && pre_fb_nwins && sf.bits == 0 && npoints == pre_n && tune.chunk == 0 && tune.max_scratch == 0 && fixed_fits(npoints, scalars)) {
             invoke_fixed(out, npoints, scalars, mont);
             return;
         }
 
         const bool pts_dev = is_device_pointer(points), sc_dev = is_device_pointer(scalars);
         const bool host = !pts_dev || !sc_dev;
-        const size_t chunk = choose_chunk(npoints, (pts_dev ? 0 : ffi_affine_sz) + (sc_dev ? 0 : SCALAR_BYTES));
+        const size_t chunk = choose_chunk(npoints, (pts_dev ? 0 : ffi_affine_sz) + (sc_dev ? 0 : sf.stride), sf.plan_bits());
         const std::vector<size_t> cb = chunk_bounds(npoints, chunk);
         const size_t nchunks = cb.size() - 1;
         const size_t in_stride = preconverted ? conv_stride() : ffi_affine_sz;     // bytes between input records
@@ -939,14 +990,14 @@ public:
         std::vector<layout> layouts(nchunks);
         size_t need = 0, longest = 0;
         for (size_t c = 0; c < nchunks; c++) {
-            plans[c] = make_plan(cb[c + 1] - cb[c], FRp::NBITS, tune);
+            plans[c] = make_plan(cb[c + 1] - cb[c], sf.plan_bits(), tune);
             if (plans[c].nwins > MAX_WINS) HIP_OK(hipErrorInvalidValue);
             layouts[c] = make_layout(plans[c], !preconverted);
             need = std::max(need, layouts[c].total); longest = std::max(longest, cb[c + 1] - cb[c]);
         }
         reserve(need);
         reserve_sums(nchunks * MAX_WINS + 1);                    // (+ the small sizes' flag word behind the sums of a one-chunk MSM)
-        const size_t st_pts = align_up(pts_dev ? 0 : longest * ffi_affine_sz), st_sc = align_up(sc_dev ? 0 : longest * SCALAR_BYTES);
+        const size_t st_pts = align_up(pts_dev ? 0 : longest * ffi_affine_sz), st_sc = align_up(sc_dev ? 0 : longest * sf.stride);
         if (host) { reserve_stage(2 * (st_pts + st_sc)); if (nchunks > 1) need_cpy(); }
 
         for (size_t c = 0; c < nchunks; c++) {
@@ -955,7 +1006,7 @@ public:
             const layout& l = layouts[c];
             const unsigned sb = c & 1;
             const unsigned char* d_points = (const unsigned char*)points + lo * in_stride;
-            const u32* d_scalars = (const u32*)((const unsigned char*)scalars + lo * SCALAR_BYTES);
+            const u32* d_scalars = (const u32*)((const unsigned char*)scalars + lo * sf.stride);
             if (host) {
                 // copies of chunk c: scalars first (the sort only needs them).  With more than one chunk they run
                 // on the copy stream, under the arithmetic of chunk c-1; pageable source memory makes the call
@@ -965,7 +1016,7 @@ public:
                 unsigned char* sp = stage + sb * (st_pts + st_sc);
                 if (nchunks > 1 && c >= 2) HIP_OK(hipStreamWaitEvent(cpy, ev_chunkdone[sb], 0));    // chunk c-2 is done with this set
                 if (!sc_dev) {
-                    HIP_OK(hipMemcpyAsync(sp + st_pts, d_scalars, cn * SCALAR_BYTES, hipMemcpyHostToDevice, cs));
+                    HIP_OK(hipMemcpyAsync(sp + st_pts, d_scalars, cn * sf.stride, hipMemcpyHostToDevice, cs));
                     d_scalars = (const u32*)(sp + st_pts);
                 }
                 if (!pts_dev) {
@@ -979,7 +1030,7 @@ public:
             }
             // (chunks of different lengths have layouts of their own: harmless, every sort set of an MSM is
             // either written on the main stream or behind an event recorded on it after the previous MSM)
-            enqueue(p, l, d_points, in_stride, preconverted, d_scalars, mont, h_sums + c * MAX_WINS, c == 0, 0, 0, false, nchunks == 1);
+            enqueue(p, l, d_points, in_stride, preconverted, d_scalars, mont, h_sums + c * MAX_WINS, c == 0, 0, 0, false, nchunks == 1, sf);
             if (host && nchunks > 1) HIP_OK(hipEventRecord(ev_chunkdone[sb], stream));
         }
         HIP_OK(hipStreamSynchronize(stream));
@@ -987,7 +1038,7 @@ public:
         // the piece tree left a bucket with more pieces than it takes (skewed scalars): the fan-in tree over the records it
         // left, the bucket sums again (single chunk: the piece tree is for sizes far below a chunk)
         if (piece_pending && *h_flag_cur != 0) {
-            enqueue(plans[0], layouts[0], nullptr, in_stride, preconverted, nullptr, mont, h_sums, false, 0, 0, true);
+            enqueue(plans[0], layouts[0], nullptr, in_stride, preconverted, nullptr, mont, h_sums, false, 0, 0, true, false, sf);
             HIP_OK(hipStreamSynchronize(stream));
             last_redo++;
         }

@@ -117,6 +117,81 @@ void k_breakdown(u32* __restrict__ digits, const u32* __restrict__ scalars,
 }
 
 // ---------------------------------------------------------------------------
+// SHORT scalars (include/sppark_amd_short.h): the caller declares b < NBITS - 1 significant bits and a stride of
+// 4 * stride_words bytes; plain little-endian integers, no Montgomery form, no fold.  The plan is made for nbits = b + 1:
+// the extra bit is zero in every scalar, so the top window's digit never exceeds its half and the signed recoding closes
+// without the r - s fold (flip = false) -- the same argument as the folded full-width scalar, whose top bit is zero.
+// Only the nw = ceil(b / 32) words that hold the b bits are read -- never more than the stride -- and the top one is
+// masked to b bits: what a caller leaves above bit b is not observable.
+// The loads are pieces of up to four words, each ONE access of a type that is only 4-byte aligned (the base of a stride
+// that is no power of two is): the HSA target runs in unaligned-access mode and the compiler issues
+// global_load_dword / x2 / x3 / x4 for them.  (A stride of 4, 8 or 16 bytes with all its words in use is one load.)
+// ---------------------------------------------------------------------------
+template<int K> struct __attribute__((packed, aligned(4))) short_piece { u32 w[K]; };
+
+// words [0, nw) of scalar i into v[0, NW), zeros above; NW = nw rounded up to a power of two (1, 2, 4, 8)
+template<int NW>
+SPPARK_DEVFN void load_scalar_short(u32 (&v)[NW], const u32* scalars, size_t i, unsigned stride_words, unsigned nw, unsigned b)
+{
+    const u32* s = scalars + i * stride_words;
+    if constexpr (NW == 1) v[0] = s[0];
+    else if constexpr (NW == 2) {
+        const short_piece<2> q = *reinterpret_cast<const short_piece<2>*>(s);
+        v[0] = q.w[0]; v[1] = q.w[1];
+    } else {
+        #pragma unroll
+        for (int k = 0; k < NW; k++) v[k] = 0;
+        #pragma unroll
+        for (int p = 0; p < NW; p += 4) {
+            // (nw > NW / 2: every piece but the last is whole; the branch is uniform, nw is a kernel argument)
+            if (p + 4 <= (int)nw) {
+                const short_piece<4> q = *reinterpret_cast<const short_piece<4>*>(s + p);
+                v[p] = q.w[0]; v[p+1] = q.w[1]; v[p+2] = q.w[2]; v[p+3] = q.w[3];
+            } else if (p + 3 == (int)nw) {
+                const short_piece<3> q = *reinterpret_cast<const short_piece<3>*>(s + p);
+                v[p] = q.w[0]; v[p+1] = q.w[1]; v[p+2] = q.w[2];
+            } else if (p + 2 == (int)nw) {
+                const short_piece<2> q = *reinterpret_cast<const short_piece<2>*>(s + p);
+                v[p] = q.w[0]; v[p+1] = q.w[1];
+            } else if (p + 1 == (int)nw) v[p] = s[p];
+        }
+    }
+    const u32 top = (b & 31) ? (1u << (b & 31)) - 1 : ~0u;      // bits of word nw - 1 below bit b
+    #pragma unroll
+    for (int k = 0; k < NW; k++) if (k + 1 == (int)nw) v[k] &= top;
+}
+
+// power-of-two word count the kernel is instantiated for
+static inline constexpr unsigned short_words_pow2(unsigned nw) { return nw <= 1 ? 1 : nw <= 2 ? 2 : nw <= 4 ? 4 : 8; }
+
+// one scalar: load, mask, stage the NW words and two zero words through |stage| (k -> the work item's staged word k),
+// digits of windows [w_begin, w_begin + w_count).  nbits = b + 1; recode_digits reads words up to (b >> 5) + 1 <= NW + 1.
+template<int NW, class Stage>
+SPPARK_DEVFN void breakdown_short_item(u32* digits, const u32* scalars, size_t n, size_t i, Stage stage,
+                                       unsigned nwins, unsigned nbits, unsigned stride_words, unsigned w_begin, unsigned w_count)
+{
+    const unsigned b = nbits - 1, nw = (b + 31) / 32;
+    u32 v[NW];
+    load_scalar_short<NW>(v, scalars, i, stride_words, nw, b);
+    #pragma unroll
+    for (int k = 0; k < NW; k++) stage(k) = v[k];
+    stage(NW) = 0; stage(NW + 1) = 0;
+    recode_digits(digits, n, i, [&](unsigned k) { return stage(k); }, false, nwins, nbits, w_begin, w_count);
+}
+
+template<int NW>
+__global__ __launch_bounds__(256)
+void k_breakdown_short(u32* __restrict__ digits, const u32* __restrict__ scalars,
+                       unsigned n, unsigned nwins, unsigned nbits, unsigned stride_words, unsigned w_begin, unsigned w_count)
+{
+    __shared__ u32 limbs[NW + 2][256];                  // transposed, as k_breakdown's: lane = bank, dynamic word index without scratch
+    const unsigned tid = threadIdx.x;
+    for (unsigned i = blockIdx.x * 256 + tid; i < n; i += gridDim.x * 256)
+        breakdown_short_item<NW>(digits, scalars, n, i, [&](unsigned k) -> u32& { return limbs[k][tid]; },
+                                 nwins, nbits, stride_words, w_begin, w_count);
+}
+
+// ---------------------------------------------------------------------------
 // accumulate (level 0).  Work item (chunk, window) owns entries
 // [chunk*L, chunk*L + L) of window w's grouped list.  Runs that touch the
 // chunk's ends are handed to the next level as (key, sum) records (slot 0 =

@@ -83,6 +83,7 @@ struct msm_call {
     size_t stride = 0;                  // bytes between wire points
     bool aligned16 = false;             // ... whose base is 16-byte aligned
     unsigned top_cut = 0;               // tuning builds: "sb sp" of the subset-sum top as two digits (0 = bucket_top_cut)
+    unsigned short_bits = 0;            // short scalars (k_breakdown_short): every scalar is below 2^short_bits; 0 = full width, folded below r/2
 };
 
 struct msm_route {
@@ -113,7 +114,9 @@ static inline unsigned div_up(size_t a, size_t b) { return (unsigned)((a + b - 1
 
 // pieces per bucket the piece tree of a small MSM takes, 0 = the record list goes through k_join_runs / the fan-in tree:
 // one window group, not the fixed-base window, buckets longer than the join's walk, at most 2^10 pieces
-static inline unsigned piece_tree_cmax(const msm_plan& p, const msm_switches& sw, unsigned fb_n, const uint32_t* scalar_mod, unsigned scalar_words)
+// (|short_bits|: msm_call)
+static inline unsigned piece_tree_cmax(const msm_plan& p, const msm_switches& sw, unsigned fb_n, const uint32_t* scalar_mod, unsigned scalar_words,
+                                       unsigned short_bits = 0)
 {
     if (p.G > 1 || fb_n || sw.no_piece_tree) return 0;
     if ((size_t)p.n / p.NB <= (size_t)4 * p.L) return 0;
@@ -122,9 +125,17 @@ static inline unsigned piece_tree_cmax(const msm_plan& p, const msm_switches& sw
     // windows: 0.43 n in one bucket against the average n / 8.  The tree is sized for that bucket too (the other short
     // windows at the top are at most twice the average: within piece_cmax's head-room).
     const unsigned off_top = p.nbits - window_len(p.nwins - 1, p.nwins, p.nbits);
-    long double r = 0;
-    for (int i = (int)scalar_words - 1; i >= 0; i--) r = r * 4294967296.0L + (long double)scalar_mod[i];
-    long double frac = ldexpl(1.0L, (int)off_top) / (r / 2);
+    // Short scalars are not folded: the bound is 2^short_bits instead of r/2 (the plan's nbits = short_bits + 1: at most
+    // half of the top window's digit range is in use, so its fullest bucket holds up to twice the average -- or all n when
+    // the top window is that one bit alone).
+    long double bound;
+    if (short_bits) bound = ldexpl(1.0L, (int)short_bits);
+    else {
+        long double r = 0;
+        for (int i = (int)scalar_words - 1; i >= 0; i--) r = r * 4294967296.0L + (long double)scalar_mod[i];
+        bound = r / 2;
+    }
+    long double frac = ldexpl(1.0L, (int)off_top) / bound;
     if (frac > 1.0L) frac = 1.0L;
     const size_t top_pieces = (size_t)((long double)p.n * frac / p.L) + 2;
     const unsigned c = std::max(piece_cmax((size_t)p.n / p.NB / p.L + 1), piece_cmax_exact(top_pieces + top_pieces / 4 + 4));
@@ -195,7 +206,7 @@ static inline msm_route make_route(const msm_plan& p, const msm_tunables& tune, 
     // bucket with more than cmax pieces (skewed scalars) keeps its records and raises the flag; the fan-in tree is NOT
     // queued behind it -- ten launches that find nothing to do are 50 us -- but run afterwards by invoke() when the flag,
     // which comes back with the window sums, is set.  (One window group, whose offsets are all still there.)
-    r.piece_cmax = c.may_defer ? piece_tree_cmax(p, sw, c.fb_n, f.scalar_mod, f.scalar_words) : 0;
+    r.piece_cmax = c.may_defer ? piece_tree_cmax(p, sw, c.fb_n, f.scalar_mod, f.scalar_words, c.short_bits) : 0;
     // windows of up to 256 buckets (MSMs of up to 2^16 points): the subset sums straight from the buckets, then the parts of a
     // window (msm_coop_kernels.hpp k_bucket_small_bits_coop); needs the offsets of every window: one window group
     r.small_sums = coop && !multi && c.fb_n == 0 && p.NB <= SMALL_SUMS_MAX_NB && p.NB >= 2 && tune.K1 == 0 && tune.top == 0

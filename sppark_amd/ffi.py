@@ -140,6 +140,17 @@ def load(name):
         L.sppark_msm_scratch_bytes.argtypes = [vp]
         L.sppark_msm_scratch_bytes.restype = sz
         L.sppark_msm_plan.argtypes = [vp, sz, ctypes.POINTER(ctypes.c_uint * 8)]
+        # include/sppark_amd_short.h: scalars of a declared bit length
+        L.sppark_msm_invoke_bits.argtypes = [vp, vp, vp, sz, vp, cu, sz, sz]
+        L.sppark_msm_invoke_bits.restype = _Error
+        L.sppark_msm_reserve_bits.argtypes = [vp, sz, sz, ci, ci, cu, sz]
+        L.sppark_msm_reserve_bits.restype = _Error
+        L.sppark_msm_plan_bits.argtypes = [vp, sz, cu, ctypes.POINTER(ctypes.c_uint * 8)]
+        L.mult_pippenger_inf_bits.argtypes = [vp, vp, sz, vp, cu, sz, sz]
+        L.mult_pippenger_inf_bits.restype = _Error
+        if name not in NO_G2:
+            L.mult_pippenger_fp2_inf_bits.argtypes = [vp, vp, sz, vp, cu, sz, sz]
+            L.mult_pippenger_fp2_inf_bits.restype = _Error
         L.sppark_g1_jacobian_sum.argtypes = [vp, vp, sz]
         L.sppark_g1_to_affine.argtypes = [vp, vp]
         L.sppark_g1_generate.argtypes = [vp, sz, sz, ctypes.c_uint64]

@@ -25,8 +25,52 @@ def _npoints(points, stride):
     return total // stride
 
 
-def multi_scalar_mult_arkworks(points, scalars, curve="bls12_381", ffi_affine_sz=None):
+FR_BITS = {"bls12_381": 255, "bn254": 254, "bls12_377": 253, "pallas": 255, "vesta": 255}     # bit length of the scalar field's modulus
+
+
+def _item_bytes(x):
+    if hasattr(x, "element_size"):                      # torch tensor
+        return int(x.element_size())
+    return int(x.dtype.itemsize)
+
+
+def _is_word_dtype(x):
+    return str(x.dtype).split(".")[-1] in ("uint32", "uint64")
+
+
+def short_scalar_form(scalars, scalar_bits, scalar_stride=None, curve="bls12_381"):
+    """(scalar_bits, scalar_stride) of a short-scalar call (include/sppark_amd_short.h), checked against the contract
+    without loading a library: ValueError outside it.  The stride defaults to the row size of a 2-D array / tensor, or the
+    item size of a 1-D uint32 / uint64 one."""
+    bits = int(scalar_bits)
+    if scalar_stride is None:
+        shape = tuple(scalars.shape)
+        if len(shape) == 2:
+            scalar_stride = int(shape[1]) * _item_bytes(scalars)
+        elif len(shape) == 1 and _is_word_dtype(scalars):
+            scalar_stride = _item_bytes(scalars)
+        else:
+            raise ValueError("scalar_stride is needed: the scalars are neither a 2-D array (one row per scalar) nor a 1-D uint32 / uint64 one")
+    stride = int(scalar_stride)
+    top = FR_BITS[curve] - 2
+    if not 1 <= bits <= top:
+        raise ValueError("scalar_bits must be 1..%d for %s (full-width scalars: leave scalar_bits out)" % (top, curve))
+    if stride % 4 or not 4 * ((bits + 31) // 32) <= stride <= 32:
+        raise ValueError("scalar_stride must be a multiple of 4 in [%d, 32] for %d-bit scalars" % (4 * ((bits + 31) // 32), bits))
+    return bits, stride
+
+
+def _check_short_base(address, stride):
+    if address % (stride if stride in (4, 8, 16) else 4):
+        raise ValueError("the scalars must be aligned to their stride of 4, 8 or 16 bytes (4 bytes for the other strides)")
+
+
+def multi_scalar_mult_arkworks(points, scalars, curve="bls12_381", ffi_affine_sz=None, scalar_bits=None, scalar_stride=None):
     """mult_pippenger_inf (poc/msm-cuda/src/lib.rs:46-82).
+
+    scalar_bits / scalar_stride: short scalars (mult_pippenger_inf_bits, include/sppark_amd_short.h) -- plain
+    little-endian integers of scalar_bits significant bits, scalar_stride bytes apart (default: the row size of a 2-D
+    array, the item size of a 1-D uint32 / uint64 one); the result is the MSM of s_i mod 2^scalar_bits.
 
     points : buffer of Affine_inf_t records (X | Y | infinity flag), stride
              ffi_affine_sz (default: 2*sizeof(fp) + 8, the arkworks layout)
@@ -34,15 +78,20 @@ def multi_scalar_mult_arkworks(points, scalars, curve="bls12_381", ffi_affine_sz
     returns the Jacobian result X|Y|Z as a uint8 array (144 B / 96 B).
     Buffers may be numpy arrays or torch tensors (host or device).
     """
+    bits, ss = (None, 32) if scalar_bits is None else short_scalar_form(scalars, scalar_bits, scalar_stride, curve)    # (refused before a library is loaded)
     L = ffi.load(curve)
     fb = FP_BYTES[curve]
     stride = ffi_affine_sz or (2 * fb + 8)
     n = _npoints(points, stride)
-    if _nbytes(scalars) != 32 * n:
+    if _nbytes(scalars) != ss * n:
         raise ValueError("length mismatch")                 # lib.rs:61-63
     pp, _k1 = ffi.as_pointer(points)
     sp, _k2 = ffi.as_pointer(scalars)
     out = np.zeros(3 * fb, dtype=np.uint8)
+    if bits is not None:
+        _check_short_base(sp, ss)
+        ffi.check(L, L.mult_pippenger_inf_bits(out.ctypes.data, pp, n, sp, bits, ss, stride))
+        return out
     ffi.check(L, L.mult_pippenger_inf(out.ctypes.data, pp, n, sp, stride))
     return out
 
@@ -117,7 +166,13 @@ class MsmContext:
     def plan_groups(self, npoints):
         return int(self.L.sppark_msm_plan_groups(self.h, npoints))
 
-    def reserve(self, npoints, ffi_affine_sz, host_points=False, host_scalars=False):
+    def reserve(self, npoints, ffi_affine_sz, host_points=False, host_scalars=False, scalar_bits=None, scalar_stride=None):
+        """scalar_bits (and scalar_stride, default 4 * ceil(scalar_bits / 32)): for invoke(..., scalar_bits=) calls"""
+        if scalar_bits is not None:
+            ss = scalar_stride if scalar_stride is not None else 4 * ((int(scalar_bits) + 31) // 32)
+            bits, ss = short_scalar_form(None, scalar_bits, ss, self.curve)
+            ffi.check(self.L, self.L.sppark_msm_reserve_bits(self.h, npoints, ffi_affine_sz, int(host_points), int(host_scalars), bits, ss))
+            return
         ffi.check(self.L, self.L.sppark_msm_reserve(self.h, npoints, ffi_affine_sz,
                                                     int(host_points), int(host_scalars)))
 
@@ -130,10 +185,15 @@ class MsmContext:
     def scratch_bytes(self):
         return int(self.L.sppark_msm_scratch_bytes(self.h))
 
-    def plan(self, npoints):
+    def plan(self, npoints, scalar_bits=None):
+        """scalar_bits: the plan of a short-scalar call (sppark_msm_plan_bits) -- the first eight keys only"""
         out = (ctypes.c_uint * 8)()
-        self.L.sppark_msm_plan(self.h, npoints, ctypes.byref(out))
         keys = ("window_bits", "windows", "buckets_per_window", "run_length", "partitions", "low_bits", "fan_in", "bucket_chunk")
+        if scalar_bits is not None:
+            bits, _ = short_scalar_form(None, scalar_bits, 32, self.curve)
+            self.L.sppark_msm_plan_bits(self.h, npoints, bits, ctypes.byref(out))
+            return dict(zip(keys, [int(v) for v in out]))
+        self.L.sppark_msm_plan(self.h, npoints, ctypes.byref(out))
         d = dict(zip(keys, [int(v) for v in out]))
         self.L.sppark_msm_plan_sort(self.h, npoints, ctypes.byref(out))
         keys = ("slabs", "slab_points", "record_index_bits", "lg_slabs_per_group", "index_groups", "window_groups", "first_bucket_chunk", "piece_tree_max")
@@ -166,17 +226,29 @@ class MsmContext:
     def preloaded(self):
         return int(self.L.sppark_msm_preloaded(self.h))
 
-    def invoke(self, points, scalars, npoints=None, mont=False, ffi_affine_sz=None):
-        """points=None: the preloaded bases (invoke(out, scalars), pippenger.cuh:604-605)."""
+    def invoke(self, points, scalars, npoints=None, mont=False, ffi_affine_sz=None, scalar_bits=None, scalar_stride=None):
+        """points=None: the preloaded bases (invoke(out, scalars), pippenger.cuh:604-605).
+        scalar_bits / scalar_stride: short scalars (sppark_msm_invoke_bits, include/sppark_amd_short.h): plain integers
+        of scalar_bits significant bits, scalar_stride bytes apart (default: the row size of a 2-D array, the item size
+        of a 1-D uint32 / uint64 one); the result is the MSM of s_i mod 2^scalar_bits."""
         stride = ffi_affine_sz or 2 * self.fb
+        bits, ss = None, 32
+        if scalar_bits is not None:
+            if mont:
+                raise ValueError("short scalars are plain integers: no mont")
+            bits, ss = short_scalar_form(scalars, scalar_bits, scalar_stride, self.curve)
         if points is None:
-            n = npoints if npoints is not None else _npoints(scalars, 32)
+            n = npoints if npoints is not None else _npoints(scalars, ss)
             pp, _k1 = None, None
         else:
             n = npoints if npoints is not None else _npoints(points, stride)
             pp, _k1 = ffi.as_pointer(points)
         sp, _k2 = ffi.as_pointer(scalars)
         out = np.zeros(3 * self.fb, dtype=np.uint8)
+        if bits is not None:
+            _check_short_base(sp, ss)
+            ffi.check(self.L, self.L.sppark_msm_invoke_bits(self.h, out.ctypes.data, pp, n, sp, bits, ss, stride))
+            return out
         ffi.check(self.L, self.L.sppark_msm_invoke(self.h, out.ctypes.data, pp, n, sp, int(mont), stride))
         return out
 
@@ -262,21 +334,27 @@ def set_g2_path(mode, curve="bls12_381"):
     ffi.check(L, L.sppark_msm_g2_path(int(mode)))
 
 
-def multi_scalar_mult_fp2_arkworks(points, scalars, curve="bls12_381", ffi_affine_sz=None):
+def multi_scalar_mult_fp2_arkworks(points, scalars, curve="bls12_381", ffi_affine_sz=None, scalar_bits=None, scalar_stride=None):
     """mult_pippenger_fp2_inf (poc/msm-cuda/src/lib.rs:84-119): MSM over G2.
+    scalar_bits / scalar_stride: short scalars, as multi_scalar_mult_arkworks (mult_pippenger_fp2_inf_bits).
 
     points : Affine_inf_t records over Fp2: X.c0|X.c1|Y.c0|Y.c1|infinity flag, stride
              ffi_affine_sz (default 4*sizeof(fp) + 8, the arkworks G2Affine layout)
     returns: Jacobian X|Y|Z, each an Fp2 element (288 B BLS12-381, 192 B bn254)"""
+    bits, ss = (None, 32) if scalar_bits is None else short_scalar_form(scalars, scalar_bits, scalar_stride, curve)
     L = ffi.load(curve)
     fb = FP_BYTES[curve]
     stride = ffi_affine_sz or 4 * fb + 8
     n = _npoints(points, stride)
-    if _nbytes(scalars) != 32 * n:
+    if _nbytes(scalars) != ss * n:
         raise ValueError("length mismatch")
     pp, _k1 = ffi.as_pointer(points)
     sp, _k2 = ffi.as_pointer(scalars)
     out = np.zeros(6 * fb, dtype=np.uint8)
+    if bits is not None:
+        _check_short_base(sp, ss)
+        ffi.check(L, L.mult_pippenger_fp2_inf_bits(out.ctypes.data, pp, n, sp, bits, ss, stride))
+        return out
     ffi.check(L, L.mult_pippenger_fp2_inf(out.ctypes.data, pp, n, sp, stride))
     return out
 

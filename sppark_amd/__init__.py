@@ -12,3 +12,4 @@ from .msm import (multi_scalar_mult, multi_scalar_mult_arkworks, multi_scalar_mu
 from .ntt import (NTT, iNTT, coset_NTT, coset_iNTT, compute_ntt, LDE, LDE_powers, LDE_expand,                  # noqa: F401
                   compute_ntt_batch, LDE_batch, NTTInputOutputOrder, NTTDirection, NTTType)
 from . import poly                                                                   # noqa: F401
+from . import circle                                                                 # noqa: F401

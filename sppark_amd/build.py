@@ -46,7 +46,9 @@ TARGETS = {
     "gl64":      ("FEATURE_GOLDILOCKS", NTT_TUS),
     "bb31":      ("FEATURE_BABY_BEAR", NTT_TUS),
     # field types without NTT parameters in the reference: polynomial primitives only
-    "m31":       ("FEATURE_MERSENNE31", ["api/poly_only_api.hip"]),
+    # (+ the circle transform, the transform of this field: include/sppark_amd_circle.h)
+    "m31":       ("FEATURE_MERSENNE31", ["api/poly_only_api.hip", "api/circle_api.hip",
+                                         "circle/k_circle.hip:SPPARK_CIRCLE_INV=0", "circle/k_circle.hip:SPPARK_CIRCLE_INV=1"]),
     "bb31x4":    ("FEATURE_BABY_BEAR_X4", ["api/poly_only_api.hip"]),
     # the reference's compile-time root conventions (ntt/parameters/goldilocks.h:7-82, baby_bear.h:7-74)
     "gl64_plonky2":   ("FEATURE_GOLDILOCKS -DGOLDILOCKS_PLONKY2", NTT_TUS),

@@ -203,6 +203,16 @@ def load(name):
         L.sppark_poly_product.restype = _Error
         L.sppark_poly_vanishing_quotient.argtypes = [sz, vp, vp, vp, vp, ctypes.c_uint32, vp]
         L.sppark_poly_vanishing_quotient.restype = _Error
+    if name == "m31":                                                            # include/sppark_amd_circle.h
+        u32 = ctypes.c_uint32
+        L.sppark_circle_ntt.argtypes = [sz, vp, u32, sz, sz, ci, ci, vp]
+        L.sppark_circle_ntt.restype = _Error
+        L.sppark_circle_lde.argtypes = [sz, vp, u32, u32, sz, ci, vp, vp]
+        L.sppark_circle_lde.restype = _Error
+        L.sppark_circle_cached_bytes.argtypes = [sz]
+        L.sppark_circle_cached_bytes.restype = sz
+        L.sppark_circle_release_cached.argtypes = [sz]
+        L.sppark_circle_release_cached.restype = _Error
     _LIBS[name] = L
     return L
 

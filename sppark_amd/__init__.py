@@ -13,3 +13,4 @@ from .ntt import (NTT, iNTT, coset_NTT, coset_iNTT, compute_ntt, LDE, LDE_powers
                   compute_ntt_batch, LDE_batch, NTTInputOutputOrder, NTTDirection, NTTType)
 from . import poly                                                                   # noqa: F401
 from . import circle                                                                 # noqa: F401
+from . import mle                                                                    # noqa: F401

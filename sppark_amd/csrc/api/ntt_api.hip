@@ -251,3 +251,4 @@ SPPARK_FFI size_t sppark_ntt_batch_launch_cols(size_t device_id, uint32_t lg_dom
 #include "field_api.hpp"
 #define SPPARK_VEC_WITH_NTT 1       // sppark_poly_product, sppark_poly_vanishing_quotient
 #include "vec_api.hpp"
+#include "mle_api.hpp"

@@ -18,3 +18,4 @@ template<class Fn> static RustError guarded(Fn&& fn)
 #include "poly_api.hpp"
 #include "field_api.hpp"
 #include "vec_api.hpp"
+#include "mle_api.hpp"

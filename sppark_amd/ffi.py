@@ -198,6 +198,15 @@ def load(name):
             fn.restype = _Error
         L.sppark_field_mul_sub.argtypes = [sz, vp, vp, vp, vp, vp, sz, vp]
         L.sppark_field_mul_sub.restype = _Error
+        u32 = ctypes.c_uint32                                                    # include/sppark_amd_mle.h
+        L.sppark_mle_fold.argtypes = [sz, vp, vp, u32, vp, ci, vp]
+        L.sppark_mle_fold.restype = _Error
+        L.sppark_mle_evaluate.argtypes = [sz, vp, vp, u32, vp, vp]
+        L.sppark_mle_evaluate.restype = _Error
+        L.sppark_mle_eq.argtypes = [sz, vp, vp, u32, vp]
+        L.sppark_mle_eq.restype = _Error
+        L.sppark_sumcheck_round.argtypes = [sz, vp, ctypes.POINTER(vp), sz, ci, u32, ci, vp]
+        L.sppark_sumcheck_round.restype = _Error
     if name in NTT_FIELDS or name in CURVES:
         L.sppark_poly_product.argtypes = [sz, vp, vp, sz, vp, sz, vp]
         L.sppark_poly_product.restype = _Error

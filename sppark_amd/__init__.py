@@ -14,3 +14,4 @@ from .ntt import (NTT, iNTT, coset_NTT, coset_iNTT, compute_ntt, LDE, LDE_powers
 from . import poly                                                                   # noqa: F401
 from . import circle                                                                 # noqa: F401
 from . import mle                                                                    # noqa: F401
+from . import merkle                                                                 # noqa: F401

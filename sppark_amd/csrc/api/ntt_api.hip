@@ -252,3 +252,4 @@ SPPARK_FFI size_t sppark_ntt_batch_launch_cols(size_t device_id, uint32_t lg_dom
 #define SPPARK_VEC_WITH_NTT 1       // sppark_poly_product, sppark_poly_vanishing_quotient
 #include "vec_api.hpp"
 #include "mle_api.hpp"
+#include "merkle_api.hpp"

@@ -19,3 +19,4 @@ template<class Fn> static RustError guarded(Fn&& fn)
 #include "field_api.hpp"
 #include "vec_api.hpp"
 #include "mle_api.hpp"
+#include "merkle_api.hpp"

@@ -207,6 +207,13 @@ def load(name):
         L.sppark_mle_eq.restype = _Error
         L.sppark_sumcheck_round.argtypes = [sz, vp, ctypes.POINTER(vp), sz, ci, u32, ci, vp]
         L.sppark_sumcheck_round.restype = _Error
+        # include/sppark_amd_merkle.h (indices: a host array of uint64, passed by address)
+        L.sppark_merkle_commit.argtypes = [sz, vp, vp, vp, u32, sz, sz, sz, ci, vp]
+        L.sppark_merkle_commit.restype = _Error
+        L.sppark_merkle_open.argtypes = [sz, vp, vp, u32, vp, sz, vp]
+        L.sppark_merkle_open.restype = _Error
+        L.sppark_merkle_gather.argtypes = [sz, vp, vp, u32, sz, sz, sz, vp, sz, vp]
+        L.sppark_merkle_gather.restype = _Error
     if name in NTT_FIELDS or name in CURVES:
         L.sppark_poly_product.argtypes = [sz, vp, vp, sz, vp, sz, vp]
         L.sppark_poly_product.restype = _Error

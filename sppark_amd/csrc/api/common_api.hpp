@@ -1,9 +1,8 @@
 // Symbols every sppark_amd library exports, mirroring util/all_gpus.cpp:65-86
-// and util/gpu_t.cuh:365-369 (SPPARK_FFI = extern "C" + default visibility).
+// and util/gpu_t.cuh:365-369 (SPPARK_FFI, api/call.hpp = extern "C" + default visibility).  One translation unit
+// per library includes this; the others include api/call.hpp alone.
 #pragma once
-#include "../util/runtime.hpp"
-
-#define SPPARK_FFI extern "C" __attribute__((visibility("default")))
+#include "call.hpp"
 
 // true iff at least one usable device (util/all_gpus.cpp:65-66)
 SPPARK_FFI bool cuda_available()

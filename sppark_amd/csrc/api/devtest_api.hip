@@ -6,12 +6,11 @@
 // reference's surface.
 #include "../msm/curve_select.hpp"
 #include "../ec/xyzz_coop.hpp"
-#include "../util/runtime.hpp"
+#include "call.hpp"
 #include <vector>
 
 using namespace sppark_amd;
 
-#define SPPARK_FFI extern "C" __attribute__((visibility("default")))
 SPPARK_FFI void drop_error_message(char* ptr) { free(ptr); }
 
 template<class F>
@@ -49,13 +48,6 @@ __global__ void k_xyzz_op(wire_bucket_m* out, const wire_bucket_m* a, const unsi
         p.madd(q, op == 2);
     }
     p.store(&out[i]);
-}
-
-template<class Fn> static RustError guarded(Fn&& fn)
-{
-    try { fn(); return rust_ok(); }
-    catch (const hip_error& e) { (void)hipGetLastError(); return rust_err(e.code(), e.what()); }
-    catch (const std::exception& e) { return rust_err(-1, e.what()); }
 }
 
 template<class F>

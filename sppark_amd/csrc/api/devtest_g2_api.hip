@@ -11,7 +11,7 @@
 //   e. sppark_devtest_g2_chain           : chains of set / madd steps by the serial class or by wave pairs
 // b - e exist on the curves with a G2 only.  Every kernel is built for work-groups of at most 128 lanes.
 #include "../msm/curve_select.hpp"
-#include "../util/runtime.hpp"
+#include "call.hpp"
 #if !defined(SPPARK_NO_G2) && !defined(SPPARK_FP2_32LIMB)       // (the A/B build of the old G2 pipeline type has no fp2x_dev)
 # define SPPARK_DEVTEST_G2 1
 # include "../msm/msm_g2c_kernels.hpp"
@@ -20,15 +20,7 @@
 
 using namespace sppark_amd;
 
-#define SPPARK_FFI extern "C" __attribute__((visibility("default")))
-
 namespace {
-template<class Fn> RustError guarded(Fn&& fn)
-{
-    try { fn(); return rust_ok(); }
-    catch (const hip_error& e) { (void)hipGetLastError(); return rust_err(e.code(), e.what()); }
-    catch (const std::exception& e) { return rust_err(-1, e.what()); }
-}
 // a device copy of |bytes| host bytes (or an uninitialised buffer when src is null); freed with the scope
 struct dev_buf {
     void* p = nullptr;

@@ -2,19 +2,11 @@
 // libsppark_<field>_devtest.so -- a TEST library, not part of the product libraries): element-wise
 // field operations on the GPU, compared with Python big-ints by tests/test_ntt_gpu.py.
 #include "../ntt/field_select.hpp"
-#include "../util/runtime.hpp"
+#include "call.hpp"
 
 using namespace sppark_amd;
 typedef ntt_fr_t fr_t;
-#define SPPARK_FFI extern "C" __attribute__((visibility("default")))
 
-template<class Fn> static RustError guarded(Fn&& fn)
-{
-    try { fn(); return rust_ok(); }
-    catch (const hip_error& e) { (void)hipGetLastError(); return rust_err(e.code(), e.what()); }
-    catch (const std::exception& e) { return rust_err(-1, e.what()); }
-    catch (...) { return rust_err(-1, "unknown exception"); }
-}
 SPPARK_FFI void drop_error_message(char* ptr) { free(ptr); }
 
 // op 0: a+b  1: a-b  2: a*b  3: a*2^k (gl64 only; k = b's low byte mod 192)  7/8: fused butterfly sum/difference

@@ -1,21 +1,20 @@
 // C entry points of the multilinear tables and sumcheck rounds over the library's field fr_t (include/sppark_amd_mle.h).
-// Included behind api/vec_api.hpp, whose argument checks (field_reject, field_check_pair, vec_ranges_meet) and whose dev_view
-// staging it shares.  The launches are those of mle/mle_route.hpp: the drivers below run what the route says.
-// Expects: fr_t, guarded(), SPPARK_FFI, select_gpu, is_device_pointer in scope.
+// The launches are those of mle/mle_route.hpp: the drivers below run what the route says.
+// Expects fr_t in scope.
 #pragma once
-#include "vec_api.hpp"
+#include "call.hpp"
 #include "../mle/mle_kernels.hpp"
 
 namespace {
 // n = 2^lg_n elements in bytes; lg_n above MLE_MAX_LG is rejected
 size_t mle_bytes(uint32_t lg_n, const std::string& who)
 {
-    if (lg_n > MLE_MAX_LG) field_reject((who + ": lg_n above " + std::to_string(MLE_MAX_LG)).c_str());
-    return vec_bytes((size_t)1 << lg_n, who);
+    if (lg_n > MLE_MAX_LG) reject(who + ": lg_n above " + std::to_string(MLE_MAX_LG));
+    return elems_bytes((size_t)1 << lg_n, sizeof(fr_t), who.c_str());
 }
 int mle_order(int order, const std::string& who)
 {
-    if (order != MLE_LOW && order != MLE_HIGH) field_reject((who + ": unknown order").c_str());
+    if (order != MLE_LOW && order != MLE_HIGH) reject(who + ": unknown order");
     return order;
 }
 mle_route mle_route_of(const gpu_info& gpu, uint32_t lg_n, int op, unsigned rows, bool aligned16)
@@ -24,7 +23,7 @@ mle_route mle_route_of(const gpu_info& gpu, uint32_t lg_n, int op, unsigned rows
     c.elem_bytes = sizeof(fr_t); c.lg_n = lg_n; c.cus = (unsigned)gpu.prop.multiProcessorCount; c.op = op; c.rows = rows;
     c.aligned16 = aligned16;
     const mle_route r = make_mle_route(c);
-    if (r.invalid) field_reject("sppark_mle: no route");
+    if (r.invalid) reject("sppark_mle: no route");
     return r;
 }
 bool mle_aligned16(std::initializer_list<const void*> ps)
@@ -51,29 +50,27 @@ void mle_fold_any(size_t device_id, void* out, const void* in, uint32_t lg_n, co
 {
     const std::string who("sppark_mle_fold");
     const size_t bytes = mle_bytes(lg_n, who);
-    if (lg_n == 0) field_reject((who + ": lg_n == 0 (nothing to bind)").c_str());
+    if (lg_n == 0) reject(who + ": lg_n == 0 (nothing to bind)");
     mle_order(order, who);
-    if (out == nullptr || in == nullptr || r == nullptr) field_reject((who + ": NULL buffer").c_str());
+    if (out == nullptr || in == nullptr || r == nullptr) reject(who + ": NULL buffer");
     const size_t half = (size_t)1 << (lg_n - 1);
-    if (!(order == MLE_HIGH && out == in) && vec_ranges_meet(out, bytes / 2, in, bytes))
-        field_reject((who + (order == MLE_HIGH ? ": buffers overlap partially (HIGH: out must be identical to in or disjoint from it)"
-                                                : ": buffers overlap (LOW: out must be disjoint from in)")).c_str());
-    if (vec_ranges_meet(out, bytes / 2, r, sizeof(fr_t))) field_reject((who + ": r may not overlap out").c_str());
+    if (!(order == MLE_HIGH && out == in) && ranges_meet(out, bytes / 2, in, bytes))
+        reject(who + (order == MLE_HIGH ? ": buffers overlap partially (HIGH: out must be identical to in or disjoint from it)"
+                                         : ": buffers overlap (LOW: out must be disjoint from in)"));
+    if (ranges_meet(out, bytes / 2, r, sizeof(fr_t))) reject(who + ": r may not overlap out");
     const gpu_info& gpu = select_gpu((int)device_id);
 
-    fr_t rval = vec_zero();
+    fr_t rval;
+    memset(&rval, 0, sizeof(rval));
     const fr_t* rptr = nullptr;
     if (is_device_pointer(r)) rptr = (const fr_t*)r; else memcpy(&rval, r, sizeof(rval));
-    const bool all_dev = is_device_pointer(out) && is_device_pointer(in);
-    dev_view vin(all_dev ? nullptr : in, all_dev ? 0 : half * 2, true, s), vout(all_dev ? nullptr : out, all_dev ? 0 : half, false, s);
-    fr_t* d_out = all_dev ? (fr_t*)out : vout.d;
-    const fr_t* d_in = all_dev ? (const fr_t*)in : vin.d;
+    call_scope sc(s);
+    const fr_t* d_in = sc.in<fr_t>(in, half * 2);
+    fr_t* d_out = sc.out<fr_t>(out, half);                      // (half the size of in: on the host a buffer of its own even when out == in)
     const mle_route route = mle_route_of(gpu, lg_n, MLE_OP_FOLD, 0, mle_aligned16({d_out, d_in}));
     if (order == MLE_HIGH) mle_fold_launch<true>(route.steps[0], d_out, d_in, rval, rptr, half, s);
     else                   mle_fold_launch<false>(route.steps[0], d_out, d_in, rval, rptr, half, s);
-    if (all_dev) { if (s == nullptr) HIP_OK(hipStreamSynchronize(s)); return; }
-    if (vout.owned) vout.flush(); else HIP_OK(hipStreamSynchronize(s));
-    vin.done(); vout.done();
+    sc.finish();
 }
 
 void mle_bind_launch(const mle_step& st, fr_t* out, const fr_t* in, const fr_t* pt, hipStream_t s)
@@ -90,9 +87,9 @@ void mle_evaluate_any(size_t device_id, void* ret, const void* in, uint32_t lg_n
 {
     const std::string who("sppark_mle_evaluate");
     const size_t bytes = mle_bytes(lg_n, who), n = (size_t)1 << lg_n;
-    if (ret == nullptr || in == nullptr || (lg_n && point == nullptr)) field_reject((who + ": NULL buffer").c_str());
-    if (vec_ranges_meet(ret, sizeof(fr_t), in, bytes) || (lg_n && vec_ranges_meet(ret, sizeof(fr_t), point, lg_n * sizeof(fr_t))))
-        field_reject((who + ": ret may not overlap in or point").c_str());
+    if (ret == nullptr || in == nullptr || (lg_n && point == nullptr)) reject(who + ": NULL buffer");
+    if (ranges_meet(ret, sizeof(fr_t), in, bytes) || (lg_n && ranges_meet(ret, sizeof(fr_t), point, lg_n * sizeof(fr_t))))
+        reject(who + ": ret may not overlap in or point");
     const gpu_info& gpu = select_gpu((int)device_id);
 
     if (lg_n == 0) {
@@ -100,43 +97,43 @@ void mle_evaluate_any(size_t device_id, void* ret, const void* in, uint32_t lg_n
         HIP_OK(hipStreamSynchronize(s));
         return;
     }
-    dev_view vin(in, n, true, s), vpt(point, lg_n, true, s);
-    const mle_route route = mle_route_of(gpu, lg_n, MLE_OP_EVALUATE, 0, mle_aligned16({vin.d}));
-    pooled_scratch buf(route.scratch_elems * sizeof(fr_t));
-    fr_t* slot = (fr_t*)buf.p;                          // every pass writes behind the one before it; the last one one element
-    const fr_t* src = vin.d;
+    call_scope sc(s);
+    const fr_t* src = sc.in<fr_t>(in, n);
+    const fr_t* d_pt = sc.in<fr_t>(point, lg_n);
+    const mle_route route = mle_route_of(gpu, lg_n, MLE_OP_EVALUATE, 0, mle_aligned16({src}));
+    fr_t* slot = (fr_t*)sc.scratch(route.scratch_elems * sizeof(fr_t));    // every pass writes behind the one before it; the last one one element
     const bool ret_dev = is_device_pointer(ret);
     for (unsigned i = 0; i < route.nsteps; i++) {
         const mle_step& st = route.steps[i];
         fr_t* dst = i + 1 == route.nsteps && ret_dev ? (fr_t*)ret : slot;
-        mle_bind_launch(st, dst, src, vpt.d + st.var_base, s);
+        mle_bind_launch(st, dst, src, d_pt + st.var_base, s);
         src = slot; slot += st.writes;
     }
-    if (!ret_dev) HIP_OK(hipMemcpyAsync(ret, src, sizeof(fr_t), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
-    vin.done(); vpt.done(); buf.done();
+    if (!ret_dev) sc.copy_out(ret, src, sizeof(fr_t));
+    sc.finish(true);
 }
 
 void mle_eq_any(size_t device_id, void* out, const void* point, uint32_t lg_n, hipStream_t s)
 {
     const std::string who("sppark_mle_eq");
     const size_t bytes = mle_bytes(lg_n, who), n = (size_t)1 << lg_n;
-    if (out == nullptr || (lg_n && point == nullptr)) field_reject((who + ": NULL buffer").c_str());
-    if (lg_n && vec_ranges_meet(out, bytes, point, lg_n * sizeof(fr_t))) field_reject((who + ": out may not overlap point").c_str());
+    if (out == nullptr || (lg_n && point == nullptr)) reject(who + ": NULL buffer");
+    if (lg_n && ranges_meet(out, bytes, point, lg_n * sizeof(fr_t))) reject(who + ": out may not overlap point");
     const gpu_info& gpu = select_gpu((int)device_id);
 
-    dev_view vpt(point, lg_n, true, s), vout(out, n, false, s);
-    const mle_route route = mle_route_of(gpu, lg_n, MLE_OP_EQ, 0, mle_aligned16({vout.d}));
+    call_scope sc(s);
+    const fr_t* d_pt = sc.in<fr_t>(point, lg_n);
+    fr_t* d_out = sc.out<fr_t>(out, n);
+    const mle_route route = mle_route_of(gpu, lg_n, MLE_OP_EQ, 0, mle_aligned16({d_out}));
     const mle_step& st = route.steps[0];
     const dim3 grid(st.grid), block(st.block);
     bool launched = false;
     if constexpr (sizeof(fr_t) < 16) {
-        if (!st.vec) { hipLaunchKernelGGL((k_mle_eq<fr_t, false>), grid, block, 0, s, vout.d, vpt.d, lg_n, st.tile_lg, st.tiles); launched = true; }
+        if (!st.vec) { hipLaunchKernelGGL((k_mle_eq<fr_t, false>), grid, block, 0, s, d_out, d_pt, lg_n, st.tile_lg, st.tiles); launched = true; }
     }
-    if (!launched) hipLaunchKernelGGL((k_mle_eq<fr_t, true>), grid, block, 0, s, vout.d, vpt.d, lg_n, st.tile_lg, st.tiles);
+    if (!launched) hipLaunchKernelGGL((k_mle_eq<fr_t, true>), grid, block, 0, s, d_out, d_pt, lg_n, st.tile_lg, st.tiles);
     HIP_OK(hipGetLastError());
-    if (vout.owned) vout.flush(); else HIP_OK(hipStreamSynchronize(s));
-    vpt.done(); vout.done();
+    sc.finish(true);
 }
 
 template<int NTAB, int FORM>
@@ -157,37 +154,30 @@ void sumcheck_round_any(size_t device_id, void* out, const void* const* tables, 
 {
     const std::string who("sppark_sumcheck_round");
     const size_t bytes = mle_bytes(lg_n, who), n = (size_t)1 << lg_n;
-    if (lg_n == 0) field_reject((who + ": lg_n == 0 (no pairs)").c_str());
+    if (lg_n == 0) reject(who + ": lg_n == 0 (no pairs)");
     mle_order(order, who);
-    if (form != SUMCHECK_PRODUCT && form != SUMCHECK_EQ_MUL_SUB) field_reject((who + ": unknown form").c_str());
+    if (form != SUMCHECK_PRODUCT && form != SUMCHECK_EQ_MUL_SUB) reject(who + ": unknown form");
     if (form == SUMCHECK_PRODUCT ? (ntables < 1 || ntables > SUMCHECK_MAX_TABLES) : ntables != 4)
-        field_reject((who + ": wrong ntables (PRODUCT: 1 .. 4, EQ_MUL_SUB: 4)").c_str());
-    if (out == nullptr || tables == nullptr) field_reject((who + ": NULL buffer").c_str());
-    for (size_t k = 0; k < ntables; k++) if (tables[k] == nullptr) field_reject((who + ": NULL table").c_str());
+        reject(who + ": wrong ntables (PRODUCT: 1 .. 4, EQ_MUL_SUB: 4)");
+    if (out == nullptr || tables == nullptr) reject(who + ": NULL buffer");
+    for (size_t k = 0; k < ntables; k++) if (tables[k] == nullptr) reject(who + ": NULL table");
     const unsigned rows = form == SUMCHECK_PRODUCT ? (unsigned)ntables + 1 : 4;
     const std::string lap = who + ": tables overlap partially (any two must be identical or disjoint)";
     for (size_t i = 0; i < ntables; i++) {
-        for (size_t j = i + 1; j < ntables; j++) field_check_pair(tables[i], tables[j], bytes, lap.c_str());
-        if (vec_ranges_meet(out, rows * sizeof(fr_t), tables[i], bytes)) field_reject((who + ": out may not overlap a table").c_str());
+        for (size_t j = i + 1; j < ntables; j++) same_or_disjoint(tables[i], tables[j], bytes, lap.c_str());
+        if (ranges_meet(out, rows * sizeof(fr_t), tables[i], bytes)) reject(who + ": out may not overlap a table");
     }
     const gpu_info& gpu = select_gpu((int)device_id);
 
-    // one device view per DISTINCT table (identical pointers stay identical on the device)
-    std::unique_ptr<dev_view> view[SUMCHECK_MAX_TABLES];
+    call_scope sc(s);                                           // (identical tables stay identical on the device)
     mle_tables<fr_t> tabs;
     bool aligned = true;
     for (size_t k = 0; k < SUMCHECK_MAX_TABLES; k++) {
-        if (k >= ntables) { tabs.p[k] = tabs.p[0]; continue; }
-        size_t same = k;
-        for (size_t j = 0; j < k; j++) if (tables[j] == tables[k]) { same = j; break; }
-        if (same != k) { tabs.p[k] = tabs.p[same]; continue; }
-        view[k].reset(new dev_view(tables[k], n, true, s));
-        tabs.p[k] = view[k]->d;
+        tabs.p[k] = k < ntables ? sc.in<fr_t>(tables[k], n) : tabs.p[0];
         aligned = aligned && mle_aligned16({tabs.p[k]});
     }
     const mle_route route = mle_route_of(gpu, lg_n, MLE_OP_ROUND, rows, aligned);
-    pooled_scratch buf(route.scratch_elems * sizeof(fr_t));
-    fr_t* slab = (fr_t*)buf.p;
+    fr_t* slab = (fr_t*)sc.scratch(route.scratch_elems * sizeof(fr_t));
     fr_t* sums = slab + route.steps[0].writes;
     const bool out_dev = is_device_pointer(out);
     const mle_step& st = route.steps[0];
@@ -200,10 +190,8 @@ void sumcheck_round_any(size_t device_id, void* out, const void* const* tables, 
     const mle_step& sum = route.steps[1];
     hipLaunchKernelGGL((k_sumcheck_sum<fr_t>), dim3(sum.grid), dim3(sum.block), 0, s, out_dev ? (fr_t*)out : sums, slab, sum.tiles, rows);
     HIP_OK(hipGetLastError());
-    if (!out_dev) HIP_OK(hipMemcpyAsync(out, sums, rows * sizeof(fr_t), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
-    for (auto& v : view) if (v) v->done();
-    buf.done();
+    if (!out_dev) sc.copy_out(out, sums, rows * sizeof(fr_t));
+    sc.finish(true);
 }
 }
 

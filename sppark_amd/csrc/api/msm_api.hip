@@ -94,14 +94,6 @@ struct sppark_msm_ctx { msm_impl impl; sppark_msm_ctx(int id, hipStream_t s) : i
 static void store_point(void* out, const point_t& p) { memcpy(out, &p, sizeof(p)); }
 static void store_inf(void* out) { memset(out, 0, sizeof(point_t)); }
 
-template<class Fn> static RustError guarded(Fn&& fn)
-{
-    try { fn(); return rust_ok(); }
-    catch (const hip_error& e) { (void)hipGetLastError(); return rust_err(e.code(), e.what()); }
-    catch (const std::exception& e) { return rust_err(-1, e.what()); }
-    catch (...) { return rust_err(-1, "unknown exception"); }
-}
-
 // The reference's entry points build an msm_t per call (msm/pippenger.cuh:730-747), i.e. a device
 // allocation and release of the whole scratch every time.  With GBs of scratch that costs up to
 // 100+ ms per call on a busy device, so the one-shot entry points borrow a context from a

@@ -36,7 +36,7 @@ extern template __global__ void k_ntt12<ntt_fr_t, false, false, true>(ntt_fr_t*,
 #endif
 #include "../ntt/ntt_driver.hpp"
 #ifdef SPPARK_NTT_WITH_MSM            // same .so as msm_api.hip, which already defines the common symbols
-# define SPPARK_FFI extern "C" __attribute__((visibility("default")))
+# include "call.hpp"
 #else
 # include "common_api.hpp"
 #endif
@@ -44,35 +44,18 @@ extern template __global__ void k_ntt12<ntt_fr_t, false, false, true>(ntt_fr_t*,
 using namespace sppark_amd;
 typedef ntt_fr_t fr_t;
 
-template<class Fn> static RustError guarded(Fn&& fn)
-{
-    try { fn(); return rust_ok(); }
-    catch (const hip_error& e) { (void)hipGetLastError(); return rust_err(e.code(), e.what()); }
-    catch (const std::exception& e) { return rust_err(-1, e.what()); }
-    catch (...) { return rust_err(-1, "unknown exception"); }
-}
-
 static void ntt_any(size_t device_id, void* inout, uint32_t lg, int order, int direction, int type, hipStream_t stream)
 {
     if (lg == 0) return;
-    // the arguments are checked before anything is allocated or copied: |bytes| is only meaningful (and the caller's
+    // the arguments are checked before anything is allocated or copied: the size is only meaningful (and the caller's
     // buffer only that large) for an lg the field accepts
     if (lg > fr_t::TWO_ADICITY || order < 0 || order > 3) HIP_OK(hipErrorInvalidValue);
     const gpu_info& gpu = select_gpu((int)device_id);
-    const size_t bytes = sizeof(fr_t) << lg;
-    if (is_device_pointer(inout)) {
-        ntt_engine<fr_t>::instance().run(gpu, (fr_t*)inout, lg, order, direction, type, stream);
-        if (stream == nullptr) HIP_OK(hipStreamSynchronize(stream));
-        return;
-    }
-    // host buffer: H2D, transform, D2H (NTT::Base, ntt/ntt.cuh:216-244)
-    pooled_scratch buf(bytes);                  // (util/runtime.hpp: kept between calls)
-    fr_t* d = (fr_t*)buf.p;
-    HIP_OK(hipMemcpyAsync(d, inout, bytes, hipMemcpyHostToDevice, stream));
+    // a host buffer: H2D, transform, D2H (NTT::Base, ntt/ntt.cuh:216-244); a device buffer and a stream: only enqueued
+    call_scope sc(stream);
+    fr_t* d = sc.inout<fr_t>(inout, (size_t)1 << lg);
     ntt_engine<fr_t>::instance().run(gpu, d, lg, order, direction, type, stream);
-    HIP_OK(hipMemcpyAsync(inout, d, bytes, hipMemcpyDeviceToHost, stream));
-    HIP_OK(hipStreamSynchronize(stream));
-    buf.done();
+    sc.finish();
 }
 
 SPPARK_FFI RustError compute_ntt(size_t device_id, void* inout, uint32_t lg_domain_size,
@@ -91,20 +74,18 @@ static void lde_any(size_t device_id, void* inout, uint32_t lg_domain, uint32_t 
     const size_t dom = (size_t)1 << lg_domain, ext = dom << lg_blowup;
     const bool dev = is_device_pointer(inout), aux_dev = aux_out && is_device_pointer(aux_out);
     // scratch: [tmp: dom][aux: dom, when it has to be staged][ext, when inout is a host buffer]
+    // (one buffer, and of inout only the 2^lg_domain evaluations go to the device: the scope's scratch, not its staging)
     const size_t need = dom + (aux_out && !aux_dev ? dom : 0) + (dev ? 0 : ext);
-    pooled_scratch buf(need * sizeof(fr_t));
-    fr_t* scratch = (fr_t*)buf.p;
-    {
-        fr_t* d_tmp = scratch;
-        fr_t* d_aux = aux_out ? (aux_dev ? (fr_t*)aux_out : scratch + dom) : nullptr;
-        fr_t* d_ext = dev ? (fr_t*)inout : scratch + need - ext;
-        if (!dev) HIP_OK(hipMemcpyAsync(d_ext, inout, dom * sizeof(fr_t), hipMemcpyHostToDevice, stream));
-        ntt_engine<fr_t>::instance().lde(gpu, d_ext, d_tmp, d_aux, lg_domain, lg_blowup, stream);
-        if (aux_out && !aux_dev) HIP_OK(hipMemcpyAsync(aux_out, d_aux, dom * sizeof(fr_t), hipMemcpyDeviceToHost, stream));
-        if (!dev) HIP_OK(hipMemcpyAsync(inout, d_ext, ext * sizeof(fr_t), hipMemcpyDeviceToHost, stream));
-        HIP_OK(hipStreamSynchronize(stream));
-    }
-    buf.done();
+    call_scope sc(stream);
+    fr_t* scratch = (fr_t*)sc.scratch(need * sizeof(fr_t));
+    fr_t* d_tmp = scratch;
+    fr_t* d_aux = aux_out ? (aux_dev ? (fr_t*)aux_out : scratch + dom) : nullptr;
+    fr_t* d_ext = dev ? (fr_t*)inout : scratch + need - ext;
+    if (!dev) HIP_OK(hipMemcpyAsync(d_ext, inout, dom * sizeof(fr_t), hipMemcpyHostToDevice, stream));
+    ntt_engine<fr_t>::instance().lde(gpu, d_ext, d_tmp, d_aux, lg_domain, lg_blowup, stream);
+    if (aux_out && !aux_dev) sc.copy_out(aux_out, d_aux, dom * sizeof(fr_t));
+    if (!dev) sc.copy_out(inout, d_ext, ext * sizeof(fr_t));
+    sc.finish();
 }
 SPPARK_FFI void sppark_ntt_release_cached(void)
 {
@@ -142,36 +123,26 @@ SPPARK_FFI RustError sppark_lde_expand(size_t device_id, void* d_out, const void
 // ---- batched transforms (include/sppark_amd_batch.h) ----
 static constexpr size_t BATCH_CHUNK_BYTES = (size_t)256 << 20;    // SPPARK_BATCH_CHUNK_BYTES
 
-[[noreturn]] static void batch_reject(const char* what)
-{   throw hip_error(-(int)hipErrorInvalidValue, std::string(what) + ": invalid argument");   }
-// bytes of |batch| columns of |n| elements |stride| apart ((batch - 1) * stride + n elements); rejects a size_t overflow
-static size_t batch_extent(size_t batch, size_t stride, size_t n, const char* what)
-{
-    size_t e = 0;
-    if (__builtin_mul_overflow(batch - 1, stride, &e) || __builtin_add_overflow(e, n, &e) || __builtin_mul_overflow(e, sizeof(fr_t), &e))
-        batch_reject(what);
-    return e;
-}
 // a device buffer's extent must lie inside the allocation that holds its first byte
 static void check_device_extent(const void* p, size_t bytes, const char* what)
 {
     hipDeviceptr_t base = nullptr;
     size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); batch_reject(what); }
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); reject(what); }
     const size_t off = (size_t)((const char*)p - (const char*)base);
-    if (off > size || bytes > size - off) batch_reject(what);
+    if (off > size || bytes > size - off) reject(what);
 }
 
 static void ntt_batch_any(size_t device_id, void* inout, uint32_t lg, size_t batch, size_t stride, int order, int direction, int type,
                           hipStream_t stream)
 {
-    if (lg > fr_t::TWO_ADICITY) batch_reject("sppark_ntt_batch: lg_domain_size above the field's 2-adicity");
-    if (order < 0 || order > 3) batch_reject("sppark_ntt_batch: ntt_order outside 0..3");
+    if (lg > fr_t::TWO_ADICITY) reject("sppark_ntt_batch: lg_domain_size above the field's 2-adicity");
+    if (order < 0 || order > 3) reject("sppark_ntt_batch: ntt_order outside 0..3");
     const size_t n = (size_t)1 << lg;
     if (stride == 0) stride = n;
-    if (stride < n) batch_reject("sppark_ntt_batch: stride below 2^lg_domain_size");
+    if (stride < n) reject("sppark_ntt_batch: stride below 2^lg_domain_size");
     if (batch == 0 || lg == 0) return;
-    const size_t bytes = batch_extent(batch, stride, n, "sppark_ntt_batch: extent overflows size_t");
+    const size_t bytes = cols_bytes(batch, stride, n, sizeof(fr_t), "sppark_ntt_batch", ": extent overflows size_t");
     const gpu_info& gpu = select_gpu((int)device_id);
     auto& E = ntt_engine<fr_t>::instance();
     if (is_device_pointer(inout)) {
@@ -182,8 +153,8 @@ static void ntt_batch_any(size_t device_id, void* inout, uint32_t lg, size_t bat
     }
     // host buffer: chunks of whole columns through one packed device buffer (the gaps between columns are never copied)
     const size_t col = n * sizeof(fr_t), cols = std::min(batch, std::max<size_t>(1, BATCH_CHUNK_BYTES / col));
-    pooled_scratch buf(cols * col);
-    fr_t* d = (fr_t*)buf.p;
+    call_scope sc(stream);
+    fr_t* d = (fr_t*)sc.scratch(cols * col);
     for (size_t c0 = 0; c0 < batch; c0 += cols) {
         const size_t k = std::min(cols, batch - c0);
         char* h = (char*)inout + c0 * stride * sizeof(fr_t);
@@ -193,18 +164,17 @@ static void ntt_batch_any(size_t device_id, void* inout, uint32_t lg, size_t bat
         if (stride == n) HIP_OK(hipMemcpyAsync(h, d, k * col, hipMemcpyDeviceToHost, stream));
         else HIP_OK(hipMemcpy2DAsync(h, stride * sizeof(fr_t), d, col, col, k, hipMemcpyDeviceToHost, stream));
     }
-    HIP_OK(hipStreamSynchronize(stream));
-    buf.done();
+    sc.finish();
 }
 
 static void lde_batch_any(size_t device_id, void* inout, uint32_t lg_domain, uint32_t lg_blowup, size_t batch, void* aux_out,
                           hipStream_t stream)
 {
-    if ((uint64_t)lg_domain + lg_blowup > fr_t::TWO_ADICITY) batch_reject("sppark_lde_batch: lg_domain_size + lg_blowup above the field's 2-adicity");
+    if ((uint64_t)lg_domain + lg_blowup > fr_t::TWO_ADICITY) reject("sppark_lde_batch: lg_domain_size + lg_blowup above the field's 2-adicity");
     const size_t dom = (size_t)1 << lg_domain, ext = dom << lg_blowup;
     if (batch == 0) return;
-    const size_t ext_bytes = batch_extent(batch, ext, ext, "sppark_lde_batch: extent overflows size_t");
-    const size_t aux_bytes = batch_extent(batch, dom, dom, "sppark_lde_batch: aux_out extent overflows size_t");
+    const size_t ext_bytes = cols_bytes(batch, ext, ext, sizeof(fr_t), "sppark_lde_batch", ": extent overflows size_t");
+    const size_t aux_bytes = cols_bytes(batch, dom, dom, sizeof(fr_t), "sppark_lde_batch", ": aux_out extent overflows size_t");
     const gpu_info& gpu = select_gpu((int)device_id);
     const bool dev = is_device_pointer(inout), aux_dev = aux_out && is_device_pointer(aux_out);
     if (dev) check_device_extent(inout, ext_bytes, "sppark_lde_batch: inout extends past its allocation");
@@ -213,8 +183,8 @@ static void lde_batch_any(size_t device_id, void* inout, uint32_t lg_domain, uin
     // columns per chunk, SPPARK_BATCH_CHUNK_BYTES at most (one column when a column needs more)
     const size_t per_col = (dom + (aux_out && !aux_dev ? dom : 0) + (dev ? 0 : ext)) * sizeof(fr_t);
     const size_t cols = std::min(batch, std::max<size_t>(1, BATCH_CHUNK_BYTES / per_col));
-    pooled_scratch buf(cols * per_col);
-    fr_t* d_tmp = (fr_t*)buf.p;
+    call_scope sc(stream);
+    fr_t* d_tmp = (fr_t*)sc.scratch(cols * per_col);
     fr_t* d_stage_aux = d_tmp + cols * dom;
     fr_t* d_stage_ext = d_stage_aux + (aux_out && !aux_dev ? cols * dom : 0);
     auto& E = ntt_engine<fr_t>::instance();
@@ -228,8 +198,7 @@ static void lde_batch_any(size_t device_id, void* inout, uint32_t lg_domain, uin
         if (aux_out && !aux_dev) HIP_OK(hipMemcpyAsync((fr_t*)aux_out + c0 * dom, d_aux, k * dom * sizeof(fr_t), hipMemcpyDeviceToHost, stream));
         if (!dev) HIP_OK(hipMemcpyAsync(h_ext, d_ext, k * ext * sizeof(fr_t), hipMemcpyDeviceToHost, stream));
     }
-    HIP_OK(hipStreamSynchronize(stream));
-    buf.done();
+    sc.finish();
 }
 
 SPPARK_FFI RustError sppark_ntt_batch(size_t device_id, void* inout, uint32_t lg_domain_size, size_t batch, size_t stride,

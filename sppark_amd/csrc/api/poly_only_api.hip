@@ -7,14 +7,6 @@
 using namespace sppark_amd;
 typedef ntt_fr_t fr_t;
 
-template<class Fn> static RustError guarded(Fn&& fn)
-{
-    try { fn(); return rust_ok(); }
-    catch (const hip_error& e) { (void)hipGetLastError(); return rust_err(e.code(), e.what()); }
-    catch (const std::exception& e) { return rust_err(-1, e.what()); }
-    catch (...) { return rust_err(-1, "unknown exception"); }
-}
-
 #include "poly_api.hpp"
 #include "field_api.hpp"
 #include "vec_api.hpp"

@@ -1,26 +1,12 @@
 // C entry points of the field-vector arithmetic over the library's field fr_t (include/sppark_amd_arith.h), and --
 // in the libraries that have compute_ntt (SPPARK_VEC_WITH_NTT, set by api/ntt_api.hip) -- of the polynomial product and
-// the vanishing quotient built from it and the transforms.  Included behind api/field_api.hpp, whose argument checks
-// (field_reject, field_check_pair) and whose dev_view staging it shares.
-// Expects: fr_t, guarded(), SPPARK_FFI, select_gpu, is_device_pointer in scope.
+// the vanishing quotient built from it and the transforms.
+// Expects fr_t (and, with SPPARK_VEC_WITH_NTT, ntt_engine) in scope.
 #pragma once
-#include "field_api.hpp"
+#include "call.hpp"
 #include "../poly/vec_kernels.hpp"
-#include <memory>
 
 namespace {
-// [p, p + pb) and [q, q + qb) share a byte
-bool vec_ranges_meet(const void* p, size_t pb, const void* q, size_t qb)
-{
-    const uintptr_t x = (uintptr_t)p, y = (uintptr_t)q;
-    return x < y ? y - x < pb : x - y < qb;
-}
-size_t vec_bytes(size_t len, const std::string& who)
-{
-    size_t bytes = 0;
-    if (__builtin_mul_overflow(len, sizeof(fr_t), &bytes)) field_reject((who + ": len * sizeof(element) overflows size_t").c_str());
-    return bytes;
-}
 fr_t vec_zero() { fr_t z; memset(&z, 0, sizeof(z)); return z; }
 
 template<int OP>
@@ -48,14 +34,14 @@ void field_vec_any(const char* name, int op, size_t device_id, void* out, const 
     const std::string who(name);
     const bool has_b = op != VEC_SCALE, has_c = op == VEC_MUL_SUB || op == VEC_MUL_SUB_K, has_k = op == VEC_SCALE || op == VEC_MUL_SUB_K;
     if (out == nullptr || a == nullptr || (has_b && b == nullptr) || (has_c && c == nullptr) || (has_k && k == nullptr))
-        field_reject((who + ": NULL buffer with len > 0").c_str());
-    const size_t bytes = vec_bytes(len, who);
+        reject(who + ": NULL buffer with len > 0");
+    const size_t bytes = elems_bytes(len, sizeof(fr_t), name);
     const std::string lap = who + ": buffers overlap partially (any two must be identical or disjoint)";
     const void* buf[4] = {out, a, has_b ? b : nullptr, has_c ? c : nullptr};
     for (int i = 0; i < 4; i++)
         for (int j = i + 1; j < 4; j++)
-            if (buf[i] && buf[j]) field_check_pair(buf[i], buf[j], bytes, lap.c_str());
-    if (has_k && vec_ranges_meet(out, bytes, k, sizeof(fr_t))) field_reject((who + ": k may not overlap out").c_str());
+            if (buf[i] && buf[j]) same_or_disjoint(buf[i], buf[j], bytes, lap.c_str());
+    if (has_k && ranges_meet(out, bytes, k, sizeof(fr_t))) reject(who + ": k may not overlap out");
     const gpu_info& gpu = select_gpu((int)device_id);
     const unsigned cus = (unsigned)gpu.prop.multiProcessorCount;
 
@@ -63,33 +49,12 @@ void field_vec_any(const char* name, int op, size_t device_id, void* out, const 
     const fr_t* kptr = nullptr;
     if (has_k) { if (is_device_pointer(k)) kptr = (const fr_t*)k; else memcpy(&kval, k, sizeof(kval)); }
 
-    bool all_dev = true;
-    for (int i = 0; i < 4; i++) if (buf[i] && !is_device_pointer(buf[i])) all_dev = false;
-    if (all_dev) {
-        vec_dispatch(op, cus, (fr_t*)out, (const fr_t*)a, (const fr_t*)b, (const fr_t*)c, kval, kptr, len, s);
-        if (s == nullptr) HIP_OK(hipStreamSynchronize(s));
-        return;
-    }
-    // a host buffer among them: one device view per DISTINCT buffer (identical pointers stay identical on the device)
-    std::unique_ptr<dev_view> view[4];
-    fr_t* d[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int i = 1; i < 4; i++) {
-        if (!buf[i]) continue;
-        int same = 0;
-        for (int j = 1; j < i; j++) if (buf[j] == buf[i]) same = j;
-        if (same) { d[i] = d[same]; continue; }
-        view[i].reset(new dev_view(buf[i], len, true, s));
-        d[i] = view[i]->d;
-    }
-    int alias = 0;                                              // the first input that out is (its view was made above)
-    for (int i = 3; i >= 1; i--) if (buf[i] == out) alias = i;
-    if (!alias) view[0].reset(new dev_view(out, len, false, s));
-    dev_view* res = view[alias].get();
-    d[0] = res->d;
-    vec_dispatch(op, cus, d[0], d[1], d[2], d[3], kval, kptr, len, s);
-    if (res->owned) res->flush();                               // (synchronises the stream)
-    else HIP_OK(hipStreamSynchronize(s));
-    for (int i = 0; i < 4; i++) if (view[i]) view[i]->done();
+    call_scope sc(s);                                           // (identical buffers stay identical on the device)
+    const fr_t* d[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int i = 1; i < 4; i++) if (buf[i]) d[i] = sc.in<fr_t>(buf[i], len);
+    fr_t* d_out = sc.out<fr_t>(out, len);
+    vec_dispatch(op, cus, d_out, d[1], d[2], d[3], kval, kptr, len, s);
+    sc.finish();
 }
 }
 
@@ -130,35 +95,33 @@ void poly_product_any(size_t device_id, void* out, const void* a, size_t la, con
 {
     if (la == 0 || lb == 0) return;
     const std::string who("sppark_poly_product");
-    if (out == nullptr || a == nullptr || b == nullptr) field_reject((who + ": NULL buffer with a length > 0").c_str());
-    size_t lo = 0;
-    if (__builtin_add_overflow(la, lb - 1, &lo)) field_reject((who + ": la + lb - 1 overflows size_t").c_str());
-    const size_t ob = vec_bytes(lo, who), ab = vec_bytes(la, who), bb = vec_bytes(lb, who);
+    if (out == nullptr || a == nullptr || b == nullptr) reject(who + ": NULL buffer with a length > 0");
+    const size_t lo = checked_add(la, lb - 1, who.c_str(), ": la + lb - 1 overflows size_t");
+    const size_t ob = elems_bytes(lo, sizeof(fr_t), who.c_str()), ab = elems_bytes(la, sizeof(fr_t), who.c_str()),
+                 bb = elems_bytes(lb, sizeof(fr_t), who.c_str());
     unsigned lg = 0;
     while (lg < 63 && ((size_t)1 << lg) < lo) lg++;
     if (((size_t)1 << lg) < lo || lg > fr_t::TWO_ADICITY)
-        field_reject((who + ": la + lb - 1 needs a transform above the field's 2-adicity of " + std::to_string(fr_t::TWO_ADICITY)).c_str());
-    if (vec_ranges_meet(out, ob, a, ab) || vec_ranges_meet(out, ob, b, bb))
-        field_reject((who + ": out must not overlap a or b").c_str());
+        reject(who + ": la + lb - 1 needs a transform above the field's 2-adicity of " + std::to_string(fr_t::TWO_ADICITY));
+    if (ranges_meet(out, ob, a, ab) || ranges_meet(out, ob, b, bb)) reject(who + ": out must not overlap a or b");
     const gpu_info& gpu = select_gpu((int)device_id);
     const unsigned cus = (unsigned)gpu.prop.multiProcessorCount;
     const bool square = a == b && la == lb;
     const size_t n = (size_t)1 << lg;
 
-    dev_view va(a, la, true, s), vb(square ? nullptr : b, square ? 0 : lb, true, s), vo(out, lo, false, s);
-    const fr_t* d_a = va.d;
-    const fr_t* d_b = square ? va.d : vb.d;
+    call_scope sc(s);
+    const fr_t* d_a = sc.in<fr_t>(a, la);
+    const fr_t* d_b = sc.in<fr_t>(b, lb);                       // (a square: the buffer of a)
+    fr_t* d_out = sc.out<fr_t>(out, lo);
     const fr_t zero = vec_zero();
     if (lo <= 2) {                                              // no transform: one element times one or two
-        if (la == 1) vec_launch<fr_t, VEC_SCALE>(cus, vo.d, d_b, nullptr, nullptr, zero, d_a, lb, s);
-        else         vec_launch<fr_t, VEC_SCALE>(cus, vo.d, d_a, nullptr, nullptr, zero, d_b, la, s);
-        if (vo.owned) vo.flush(); else HIP_OK(hipStreamSynchronize(s));
-        va.done(); vb.done();
+        if (la == 1) vec_launch<fr_t, VEC_SCALE>(cus, d_out, d_b, nullptr, nullptr, zero, d_a, lb, s);
+        else         vec_launch<fr_t, VEC_SCALE>(cus, d_out, d_a, nullptr, nullptr, zero, d_b, la, s);
+        sc.finish(true);
         return;
     }
     const size_t cols = square ? 1 : 2;
-    pooled_scratch buf(2 * n * sizeof(fr_t));
-    fr_t* col = (fr_t*)buf.p;
+    fr_t* col = (fr_t*)sc.scratch(2 * n * sizeof(fr_t));
     const unsigned gx = (unsigned)std::min<size_t>((n + VEC_NT * 4 - 1) / (VEC_NT * 4), (size_t)std::max(cus, 1u) * VEC_WG_PER_CU);
     hipLaunchKernelGGL(k_vec_pad<fr_t>, dim3(gx, (unsigned)cols), dim3(VEC_NT), 0, s, col, n, d_a, la, d_b, lb);
     HIP_OK(hipGetLastError());
@@ -166,10 +129,8 @@ void poly_product_any(size_t device_id, void* out, const void* a, size_t la, con
     E.run(gpu, col, lg, NTT_NR, NTT_FORWARD, NTT_STANDARD, s, nullptr, cols, n);
     vec_launch<fr_t, VEC_MUL>(cus, col, col, square ? col : col + n, nullptr, zero, nullptr, n, s);
     E.run(gpu, col, lg, NTT_RN, NTT_INVERSE, NTT_STANDARD, s);
-    HIP_OK(hipMemcpyAsync(vo.d, col, ob, hipMemcpyDeviceToDevice, s));
-    if (vo.owned) vo.flush(); else HIP_OK(hipStreamSynchronize(s));
-    va.done(); vb.done();
-    buf.done();
+    HIP_OK(hipMemcpyAsync(d_out, col, ob, hipMemcpyDeviceToDevice, s));
+    sc.finish(true);
 }
 
 // h = coefficients of (A B - C) / (x^n - 1) from the evaluations a, b, c over {w^i}
@@ -177,17 +138,18 @@ void vanishing_quotient_any(size_t device_id, void* h, const void* a, const void
 {
     const std::string who("sppark_poly_vanishing_quotient");
     if (lg > fr_t::TWO_ADICITY)
-        field_reject((who + ": lg_domain_size above the field's 2-adicity of " + std::to_string(fr_t::TWO_ADICITY)).c_str());
-    if (h == nullptr || a == nullptr || b == nullptr || c == nullptr) field_reject((who + ": NULL buffer").c_str());
-    const size_t n = (size_t)1 << lg, bytes = vec_bytes(n, who);
-    (void)vec_bytes(3 * n, who);
+        reject(who + ": lg_domain_size above the field's 2-adicity of " + std::to_string(fr_t::TWO_ADICITY));
+    if (h == nullptr || a == nullptr || b == nullptr || c == nullptr) reject(who + ": NULL buffer");
+    const size_t n = (size_t)1 << lg, bytes = elems_bytes(n, sizeof(fr_t), who.c_str());
+    (void)elems_bytes(3 * n, sizeof(fr_t), who.c_str());
     const std::string lap = who + ": h overlaps an input partially (it must be identical to one or disjoint from all)";
-    field_check_pair(h, a, bytes, lap.c_str()); field_check_pair(h, b, bytes, lap.c_str()); field_check_pair(h, c, bytes, lap.c_str());
+    same_or_disjoint(h, a, bytes, lap.c_str()); same_or_disjoint(h, b, bytes, lap.c_str()); same_or_disjoint(h, c, bytes, lap.c_str());
     const gpu_info& gpu = select_gpu((int)device_id);
     const unsigned cus = (unsigned)gpu.prop.multiProcessorCount;
 
-    pooled_scratch buf(3 * bytes);
-    fr_t* col = (fr_t*)buf.p;
+    // the three inputs go straight into the columns of the scratch and h comes straight out of it, from and to wherever they lie
+    call_scope sc(s);
+    fr_t* col = (fr_t*)sc.scratch(3 * bytes);
     const void* src[3] = {a, b, c};
     for (int j = 0; j < 3; j++) HIP_OK(hipMemcpyAsync(col + j * n, src[j], bytes, hipMemcpyDefault, s));
     auto& E = ntt_engine<fr_t>::instance();
@@ -198,8 +160,7 @@ void vanishing_quotient_any(size_t device_id, void* h, const void* a, const void
     vec_launch<fr_t, VEC_MUL_SUB_K>(cus, col, col, col + n, col + 2 * n, vanishing_inverse<fr_t>(lg), nullptr, n, s);
     if (lg) E.run(gpu, col, lg, NTT_NN, NTT_INVERSE, NTT_COSET, s);
     HIP_OK(hipMemcpyAsync(h, col, bytes, hipMemcpyDefault, s));
-    HIP_OK(hipStreamSynchronize(s));
-    buf.done();
+    sc.finish(true);
 }
 }
 

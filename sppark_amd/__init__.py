@@ -15,3 +15,4 @@ from . import poly                                                              
 from . import circle                                                                 # noqa: F401
 from . import mle                                                                    # noqa: F401
 from . import merkle                                                                 # noqa: F401
+from . import fri                                                                    # noqa: F401

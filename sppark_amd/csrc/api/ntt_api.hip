@@ -222,3 +222,4 @@ SPPARK_FFI size_t sppark_ntt_batch_launch_cols(size_t device_id, uint32_t lg_dom
 #include "vec_api.hpp"
 #include "mle_api.hpp"
 #include "merkle_api.hpp"
+#include "fri_api.hpp"

@@ -12,3 +12,4 @@ typedef ntt_fr_t fr_t;
 #include "vec_api.hpp"
 #include "mle_api.hpp"
 #include "merkle_api.hpp"
+#include "fri_api.hpp"

@@ -214,6 +214,14 @@ def load(name):
         L.sppark_merkle_open.restype = _Error
         L.sppark_merkle_gather.argtypes = [sz, vp, vp, u32, sz, sz, sz, vp, sz, vp]
         L.sppark_merkle_gather.restype = _Error
+        # include/sppark_amd_fri.h (fold and domain: the libraries with a 2-adic domain, i.e. all but m31)
+        L.sppark_fri_reduce.argtypes = [sz, vp, vp, ci, u32, sz, sz, sz, vp, vp, ci, vp]
+        L.sppark_fri_reduce.restype = _Error
+        if name != "m31":
+            L.sppark_fri_fold.argtypes = [sz, vp, vp, u32, u32, vp, vp, ci, vp]
+            L.sppark_fri_fold.restype = _Error
+            L.sppark_fri_domain.argtypes = [sz, vp, u32, vp, ci, vp, vp]
+            L.sppark_fri_domain.restype = _Error
     if name in NTT_FIELDS or name in CURVES:
         L.sppark_poly_product.argtypes = [sz, vp, vp, sz, vp, sz, vp]
         L.sppark_poly_product.restype = _Error

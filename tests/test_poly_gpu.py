@@ -102,6 +102,41 @@ def test_poly_vs_oracle(oracle, libs, field):
     assert (d.cpu().numpy().view(c.dtype).reshape(c.shape) == O.div_by_x_minus_z(field, c, z, rotate=True)).all()
 
 
+@pytest.mark.parametrize("field", ["gl64", "bb31x4", "bls12_381"])
+def test_poly_evaluate_device_buffers(oracle, libs, field):
+    """evaluate with ret, xs and coeffs on the device, on torch's stream: the lengths of test_poly_vs_oracle, 1 and 6
+    points, coefficients that start inside a larger buffer, and once ret aliasing xs"""
+    import torch
+    from sppark_amd import poly
+    O = oracle
+    wide = field in WIDE or field == "bb31x4"
+    tile = 1024 if wide else 2048
+    lens = [1, 3, 255, 256, 257, tile - 1, tile, tile + 1, 3 * tile + 5, 256 * tile, 256 * tile + 1, 257 * tile + 77]
+    lens.append((1 << 20) + 3 if wide else (1 << 22) + 3)
+    pool = _pool(field, max(lens).bit_length())
+    xs = pool[100:106].copy()
+    view = np.int32 if field == "bb31x4" else np.int64
+    d_pool = torch.from_numpy(pool.view(view)).cuda()
+    s = torch.cuda.current_stream().cuda_stream
+
+    def back(t):
+        return t.cpu().numpy().view(pool.dtype).reshape(-1, *pool.shape[1:])
+    for k, n in enumerate(lens):
+        want = O.poly_evaluate(field, pool[:n].copy(), xs).reshape(xs.shape)
+        d_c = d_pool[:n]                                        # a view: the first n coefficients of the pool
+        for npts in (1, 6):
+            d_x = torch.from_numpy(xs[:npts].view(view)).cuda()
+            d_ret = torch.zeros_like(d_x)
+            poly.evaluate(d_ret, d_x, d_c, field=field, stream=s)
+            assert (back(d_ret) == want[:npts]).all(), (field, n, npts)
+            assert (back(d_x) == xs[:npts]).all(), (field, n, npts)
+        if k % 4 == 1 or n == lens[-1]:                         # ret is xs itself
+            d_x = torch.from_numpy(xs.view(view)).cuda()
+            poly.evaluate(d_x, d_x, d_c, field=field, stream=s)
+            assert (back(d_x) == want).all(), (field, n, "aliased")
+    assert (back(d_pool) == pool).all()                         # the coefficients are only read
+
+
 def test_poly_properties_full_size(libs):
     """Goldilocks, 2^24 coefficients (the NTT's BASELINE size): q(X)*(X - z) + r == p(X) checked at
     random points, remainder == p(z), prefix sums difference == input."""

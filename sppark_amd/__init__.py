@@ -16,3 +16,4 @@ from . import circle                                                            
 from . import mle                                                                    # noqa: F401
 from . import merkle                                                                 # noqa: F401
 from . import fri                                                                    # noqa: F401
+from . import poseidon2                                                              # noqa: F401

@@ -223,3 +223,6 @@ SPPARK_FFI size_t sppark_ntt_batch_launch_cols(size_t device_id, uint32_t lg_dom
 #include "mle_api.hpp"
 #include "merkle_api.hpp"
 #include "fri_api.hpp"
+#if defined(FEATURE_GOLDILOCKS) || defined(FEATURE_BABY_BEAR)      // the fields Poseidon2 is defined over here
+# include "poseidon2_api.hpp"
+#endif

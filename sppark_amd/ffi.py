@@ -222,6 +222,12 @@ def load(name):
             L.sppark_fri_fold.restype = _Error
             L.sppark_fri_domain.argtypes = [sz, vp, u32, vp, ci, vp, vp]
             L.sppark_fri_domain.restype = _Error
+    if name in NTT_FIELDS:                                                       # include/sppark_amd_poseidon2.h
+        u32 = ctypes.c_uint32
+        L.sppark_poseidon2_permute.argtypes = [sz, vp, vp, sz, vp, u32, u32, vp]
+        L.sppark_poseidon2_permute.restype = _Error
+        L.sppark_poseidon2_commit.argtypes = [sz, vp, vp, vp, u32, sz, sz, sz, vp, u32, u32, vp]
+        L.sppark_poseidon2_commit.restype = _Error
     if name in NTT_FIELDS or name in CURVES:
         L.sppark_poly_product.argtypes = [sz, vp, vp, sz, vp, sz, vp]
         L.sppark_poly_product.restype = _Error
